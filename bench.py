@@ -8,9 +8,16 @@ device.  One process per GPU; the DB is replicated, reads are
 sharded (weak scaling: per-GPU batch fixed); the only collective is the final
 all-reduce of the per-taxid tallies (RCCL).
 
-Prints ONE JSON line on rank 0 with `roofline` (HBM, algorithmic bytes per launch /
-HIP-event kernel time) and, at N=1, `cpu_baseline` (the CPU oracle on a bounded
-sample of the same reads, timed on this box's host cores).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0
+(`value`, `ms_per_step`, the configuration); --dump-outputs DIR also writes what the
+last timed step computed.  --full adds everything else to the line: further windows of
+the same steps, the -p leg, `roofline` (HBM, algorithmic bytes per launch / HIP-event
+kernel time, the random-gather ceiling), the boundary-inclusive leg and, at N=1,
+`cpu_baseline` (the CPU oracle on a bounded sample of the same reads, timed on this
+box's host cores).
+
+Reads come from a pool of at most READ_POOL_STEPS steps' batches that the steps take
+in turn, so memory and set-up time do not grow with --steps.
 """
 import argparse
 import json
@@ -26,6 +33,13 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 BRANCHING = (3, 4, 4, 4, 4, 3)  # 768 species x 3 strains, 3328 nodes
+READ_POOL_STEPS = 32  # distinct batches of reads generated per read set (32 x 8 M reads of 150 bp: 18 GB, ~2 s to generate)
+DUMP_SAMPLE_READS = 1 << 19  # --dump-outputs: records of at most this many reads of the last launch (12 float64 arrays: 48 MiB)
+DUMP_SAMPLE_SEED = 4004
+# lmat_read_result fields written as they are; cand_off is left out: an offset into the -p candidate buffer, which the
+# timed (calls-only) path does not write
+DUMP_FIELDS = ("status", "match_type", "cand_kmer_cnt", "valid_kmers", "read_len", "log_avg", "stdev", "call_tid", "call_score",
+               "n_cand", "bin_sel")
 
 
 def sample_algorithmic_bytes(eng, reads, n_sample, k):
@@ -150,6 +164,31 @@ def cpu_baseline(eng, reads, n_sample, k, tmpdir):
                       "map holding the GPU table's lists for those reads' k-mers"}
 
 
+def dump_outputs(out_dir, records, first_read, counts, nomatch):
+    """--dump-outputs: what the timed path handed back for its last step, one float64 DIR/<name>.npy per array.  `records`
+    are the per-read records of the step's last launch (reads first_read, first_read + 1, ... of the read set): every field of
+    DUMP_FIELDS, for a fixed, seeded sample of DUMP_SAMPLE_READS of them when there are more; `read_index` says which reads.
+    `tally_*` are the per-taxid tallies of the timed steps (merged over the ranks), by taxid, and the three no-match counts.
+    -> {name: array} as written."""
+    n = records.size
+    idx = np.arange(n, dtype=np.int64)
+    if n > DUMP_SAMPLE_READS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).permutation(n)[:DUMP_SAMPLE_READS])
+    arrays = {"read_index": first_read + idx}
+    for f in DUMP_FIELDS:
+        arrays[f] = records[f][idx]
+    tids = sorted(counts)
+    arrays["tally_taxid"] = tids
+    arrays["tally_count"] = [counts[t][0] for t in tids]
+    arrays["tally_score"] = [counts[t][1] for t in tids]
+    arrays["tally_nomatch"] = nomatch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return arrays
+
+
 def e2e_stream(eng, reads, batch, steps, warmup, log):
     """The boundary-inclusive rate (first batch H2D start -> last result D2H complete): ASCII reads in pinned
     host memory -> H2D -> pack -> classify -> D2H of the 40-byte results, through the ring of pinned slots of
@@ -266,24 +305,30 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: further "
+                    "windows (--windows), the -p leg (value_with_candidates), `roofline`, the boundary-inclusive leg (e2e_stream) and "
+                    "the CPU baseline (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed "
+                    "as DIR/<name>.npy (float64, at most 64 MB): the per-read records of its last launch (a seeded sample of "
+                    f"{DUMP_SAMPLE_READS} reads when there are more) and the tallies of the timed steps")
     ap.add_argument("--db-gb", type=float, default=64.0, help="hash table size in GiB (BASELINE metric: 64)")
     ap.add_argument("--batch", type=int, default=8_000_000, help="reads per step per GPU (rounded up to whole launches)")
     ap.add_argument("--launch-reads", type=int, default=8_000_000, help="reads per classify launch: a step is batch / launch-reads launches (default: one launch per step; rounds 1-3 quoted launches of 2 M: --launch-reads 2000000)")
     ap.add_argument("--read-len", default="150", help="read length, or a comma list for a mixed-length batch (not the headline workload)")
-    ap.add_argument("--cpu-sample", type=int, default=120000, help="reads of the CPU baseline's sample (120 k reads = 15.7 M distinct k-mers = ~1.4 GiB of host table: DRAM-missing)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-sample", type=int, default=120000, help="--full: reads of the CPU baseline's sample (120 k reads = 15.7 M distinct k-mers = ~1.4 GiB of host table: DRAM-missing)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--list-replicas", type=int, default=1, help="copies of every distinct taxid list in the arena, one per 512-base stretch of a genome (5: 4 M lists, 250 MB -- the most 24-bit payloads address)")
     ap.add_argument("--genus-permille", type=int, default=100, help="share of every genome that is a block shared within its genus (SURVEY 8d: 100)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the boundary-inclusive (pinned host -> H2D -> classify -> D2H) leg")
-    ap.add_argument("--windows", type=int, default=5, help="the timed window of --steps steps is `value`; this many further windows of the same steps give value_median_of_windows (0: none)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the boundary-inclusive (pinned host -> H2D -> classify -> D2H) leg")
+    ap.add_argument("--windows", type=int, default=5, help="--full: the timed window of --steps steps is `value`; this many further windows of the same steps give value_median_of_windows (0: none)")
     ap.add_argument("--as-ranks", type=int, default=1, help="tests: ONE rank classifies the read sets of this many ranks one after the other (what an N-rank run must add up to)")
     ap.add_argument("--tally-out", default=None, help="tests: rank 0 writes the merged per-taxid tallies to this JSON file")
     ap.add_argument("--genome-len", type=int, default=0, help="bases per strain genome (default: sized so that the table holds ~6.4 k-mers per bucket)")
     ap.add_argument("--list-tail", default="0,0,0", help="heavy tail of taxid lists: thousandths of every genome that are blocks conserved across a whole family, phylum, superkingdom (lists of 69 / 277 / 1109 taxids): e.g. 20,10,5")
     ap.add_argument("--prune", type=int, default=0, help="run-time pruning -g N with a numeric rank map (-m): lists longer than N lose their lowest ranks first (TaxNodeStat.hpp:76-203)")
     ap.add_argument("--total-reads", type=int, default=0, help="STRONG scaling (BASELINE config 4: `50M reads sharded across 8`): this many reads in total, split evenly over the ranks and over --steps steps (overrides --batch; `scaling` becomes \"strong\")")
-    ap.add_argument("--no-cands", action="store_true", help="skip the value_with_candidates leg (the same window with -p: candidate pairs written, as bin/run_rl.sh runs it)")
-    ap.add_argument("--cands-per-read", type=int, default=32, help="capacity of the candidate buffer of the -p leg, pairs per read")
+    ap.add_argument("--no-cands", action="store_true", help="--full: skip the value_with_candidates leg (the same window with -p: candidate pairs written, as bin/run_rl.sh runs it)")
+    ap.add_argument("--cands-per-read", type=int, default=32, help="--full: capacity of the candidate buffer of the -p leg, pairs per read")
     ap.add_argument("--spawn-check", action="store_true", help="tests: every rank prints the environment it was started with and exits before touching a GPU")
     args = ap.parse_args()
 
@@ -352,7 +397,8 @@ def main():
     strong = plan_steps(args, world)
     lps = args.batch // args.launch_reads  # launches per step
     n_steps_total = args.steps + args.warmup
-    n_reads = args.batch * n_steps_total
+    n_batches = min(n_steps_total, READ_POOL_STEPS)  # step s classifies batch s % n_batches of the read set
+    n_reads = args.batch * n_batches
     read_lens = tuple(int(x) for x in str(args.read_len).split(","))
     args.read_len = read_lens[0] if len(read_lens) == 1 else "/".join(str(x) for x in read_lens)
     # rank r's reads come from seed 3003 + 7919 r; --as-ranks R (tests): this one rank takes the sets of ranks 0..R-1 in turn
@@ -413,8 +459,9 @@ def main():
     t_nm = torch.as_tensor(_Buf(base + 16 * n_ids, 3, "<i8"), device=f"cuda:{local_rank}")
 
     def run_step(rs, step):
+        first = step % n_batches * lps
         for l_ in range(lps):
-            eng.classify_async(rs, (step * lps + l_) * args.launch_reads, args.launch_reads)
+            eng.classify_async(rs, (first + l_) * args.launch_reads, args.launch_reads)
 
     def reduce_max(x):
         if dist is None:
@@ -453,9 +500,13 @@ def main():
     total_reads = args.batch * args.steps * world * args.as_ranks
     value = total_reads / dt
     merged = eng.counts() if rank == 0 else None   # the job's tallies, before the extra windows add to them
+    if args.dump_outputs and rank == 0:
+        last = (args.warmup + args.steps - 1) % n_batches * lps + lps - 1   # the last launch of the last timed step
+        dumped = dump_outputs(args.dump_outputs, eng.fetch_results(0, args.launch_reads), last * args.launch_reads, *merged)
+        log(f"outputs of the last step: {len(dumped)} arrays, {sum(a.nbytes for a in dumped.values()) / 2**20:.1f} MiB in {args.dump_outputs}")
     # further windows of the same K steps (same barriers, max over ranks): their median says how far one slow launch moved `value`
     win = []
-    for _ in range(max(args.windows, 0)):
+    for _ in range(max(args.windows, 0) if args.full else 0):
         barrier()
         t0 = time.perf_counter()
         for s in range(args.steps):
@@ -466,13 +517,14 @@ def main():
     # The same window as `value`, as bin/run_rl.sh:243 runs read_label: with -p, every read's candidate (taxid, score) pairs
     # written next to its record (8 bytes per pair on top of the algorithmic bytes).  Same steps, same barriers.
     with_cands = None
-    if not args.no_cands:
+    if args.full and not args.no_cands:
         eng.set_params(Params.run_rl(prn_all=1))
         cap = args.launch_reads * max(args.cands_per_read, 1)
 
         def run_step_c(step):
+            first = step % n_batches * lps
             for l_ in range(lps):
-                eng.classify_async_cands(reads, (step * lps + l_) * args.launch_reads, args.launch_reads, cap)
+                eng.classify_async_cands(reads, (first + l_) * args.launch_reads, args.launch_reads, cap)
 
         run_step_c(0)
         eng.sync()
@@ -494,32 +546,6 @@ def main():
             with open(args.tally_out, "w") as f:
                 json.dump({"n_gpus": world, "counts": {str(t): c for t, (c, _) in sorted(counts.items())},
                            "scores": {str(t): sc for t, (_, sc) in sorted(counts.items())}, "nomatch": nomatch}, f)
-        mean_b, mean_bucket, probes = sample_algorithmic_bytes(eng, reads, 2000, k)
-        log(f"algorithmic bytes/read = {mean_b:.0f} (reads + one 64-B bucket per distinct k-mer + result: {mean_bucket:.0f})")
-        avg_ms = classify_ms / max(launches, 1)  # dominant kernel only: classify_kernel (HBM-bound probe inside)
-        achieved = mean_b * args.launch_reads / (avg_ms * 1e-3) / 1e9
-        # every kernel of a launch: the classify kernel and what follows it (re-run classes, general decision path).  Those run on
-        # side streams beside the NEXT launch's classify kernel, so their event times overlap it and do not add up: the wall time of
-        # the timed region per launch is the honest figure
-        step_ms = dt * 1e3 / max(args.steps * args.as_ranks * lps, 1)
-        # HBM bytes per launch come from PMC counters, which only a rocprofv3 run of this command can collect
-        # (scripts/profile_gpu.sh: separate --pmc FETCH_SIZE / WRITE_SIZE passes, condensed into profiles/): the number
-        # is carried over from that committed file and labelled as such, never presented as measured in this run
-        traffic, traffic_from, frac_measured = None, None, None
-        tf = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tf):
-            try:
-                tj = json.load(open(tf))
-                same = tj.get("reads_per_launch") == args.launch_reads and tj.get("db_gib") == args.db_gb and tj.get("read_len") == args.read_len
-                if same:
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_from = f"{tj.get('from')}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on another run (kernel {tj.get('kernel_avg_ms'):.2f} ms there)"
-                    frac_measured = traffic / (tj.get("kernel_avg_ms") * 1e-3) / 1e9 / HBM_PEAK_GBS
-            except Exception:
-                traffic = None
-        g_ms, g_bytes = eng.gather_bench(1 << 28)
-        gather_gbs = g_bytes / (g_ms * 1e-3) / 1e9
-        log(f"random 64-B gather ceiling on this table: {gather_gbs:.0f} GB/s")
         out = {
             "metric": "reads/s (150 bp) vs 64 GB k-mer DB", "value": value, "unit": "reads/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / (args.steps * args.as_ranks) * 1e3,
@@ -530,17 +556,45 @@ def main():
                        "total_reads": args.batch * args.steps * world * args.as_ranks, "reads_per_step_per_gpu": args.batch, "launches_per_step": lps, "reads_per_launch": args.launch_reads, "read_len": args.read_len, "db_gib": args.db_gb,
                        "db_kmers": eng.db_size, "k": k, "parallelism": f"reads sharded x{world}, DB replicated",
                        "db_build_s": round(t_build, 2), "genus_block_permille": args.genus_permille, "list_tail_permille": list(tail), "prune_g": args.prune,
-                       "reads_past_each_class_last_launch": dict(class_flow, reads_per_launch=args.launch_reads), "list_replicas": args.list_replicas, "distinct_lists": eng.n_lists, "list_arena_mib": round(eng.arena_bytes / 2**20, 1), "reads_called": called, "nomatch": nomatch},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_from": traffic_from,
-                         "frac_measured": frac_measured,
-                         "frac_step": mean_b * args.launch_reads / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "frac_bucket_only": mean_bucket * args.launch_reads / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "algorithmic_bytes_per_read_bucket_only": mean_bucket,
-                         "kernel": "classify_kernel<160,64,256,false,false,true,false>",
-                         "kernel_avg_ms": avg_ms, "kernel_ms_per_2M_reads": avg_ms * 2e6 / args.launch_reads, "step_ms_per_launch": step_ms, "step_ms_per_2M_reads": step_ms * 2e6 / args.launch_reads, "tail_kernels_event_ms": decide_ms / max(launches, 1), "algorithmic_bytes_per_read": mean_b, "reads_per_launch": args.launch_reads,
-                         "random_64B_gather_ceiling_GBs": gather_gbs, "probe_ends": probes},
+                       "reads_past_each_class_last_launch": dict(class_flow, reads_per_launch=args.launch_reads), "list_replicas": args.list_replicas, "distinct_lists": eng.n_lists, "list_arena_mib": round(eng.arena_bytes / 2**20, 1), "reads_called": called, "nomatch": nomatch,
+                       "read_pool_batches": n_batches},
         }
+        if args.full:
+            mean_b, mean_bucket, probes = sample_algorithmic_bytes(eng, reads, 2000, k)
+            log(f"algorithmic bytes/read = {mean_b:.0f} (reads + one 64-B bucket per distinct k-mer + result: {mean_bucket:.0f})")
+            avg_ms = classify_ms / max(launches, 1)  # dominant kernel only: classify_kernel (HBM-bound probe inside)
+            achieved = mean_b * args.launch_reads / (avg_ms * 1e-3) / 1e9
+            # every kernel of a launch: the classify kernel and what follows it (re-run classes, general decision path).  Those run on
+            # side streams beside the NEXT launch's classify kernel, so their event times overlap it and do not add up: the wall time of
+            # the timed region per launch is the honest figure
+            step_ms = dt * 1e3 / max(args.steps * args.as_ranks * lps, 1)
+            # HBM bytes per launch come from PMC counters, which only a rocprofv3 run of this command can collect
+            # (scripts/profile_gpu.sh: separate --pmc FETCH_SIZE / WRITE_SIZE passes, condensed into profiles/): the number
+            # is carried over from that committed file and labelled as such, never presented as measured in this run
+            traffic, traffic_from, frac_measured = None, None, None
+            tf = os.path.join(ROOT, "profiles", "traffic_latest.json")
+            if os.path.exists(tf):
+                try:
+                    tj = json.load(open(tf))
+                    same = tj.get("reads_per_launch") == args.launch_reads and tj.get("db_gib") == args.db_gb and tj.get("read_len") == args.read_len
+                    if same:
+                        traffic = tj.get("hbm_bytes_per_launch")
+                        traffic_from = f"{tj.get('from')}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on another run (kernel {tj.get('kernel_avg_ms'):.2f} ms there)"
+                        frac_measured = traffic / (tj.get("kernel_avg_ms") * 1e-3) / 1e9 / HBM_PEAK_GBS
+                except Exception:
+                    traffic = None
+            g_ms, g_bytes = eng.gather_bench(1 << 28)
+            gather_gbs = g_bytes / (g_ms * 1e-3) / 1e9
+            log(f"random 64-B gather ceiling on this table: {gather_gbs:.0f} GB/s")
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_from": traffic_from,
+                               "frac_measured": frac_measured,
+                               "frac_step": mean_b * args.launch_reads / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "frac_bucket_only": mean_bucket * args.launch_reads / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "algorithmic_bytes_per_read_bucket_only": mean_bucket,
+                               "kernel": "classify_kernel<160,64,256,false,false,true,false>",
+                               "kernel_avg_ms": avg_ms, "kernel_ms_per_2M_reads": avg_ms * 2e6 / args.launch_reads, "step_ms_per_launch": step_ms, "step_ms_per_2M_reads": step_ms * 2e6 / args.launch_reads, "tail_kernels_event_ms": decide_ms / max(launches, 1), "algorithmic_bytes_per_read": mean_b, "reads_per_launch": args.launch_reads,
+                               "random_64B_gather_ceiling_GBs": gather_gbs, "probe_ends": probes}
         if with_cands:
             c_avg = with_cands["classify_ms"] / max(with_cands["launches"], 1)
             c_bytes = mean_b + 8.0 * with_cands["pairs_per_read"]
@@ -550,11 +604,11 @@ def main():
                 "roofline_frac": c_bytes * args.launch_reads / (c_avg * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "what": "the window of `value` again with -p (prn_all = 1): every read's candidate (taxid, score) pairs written to a device "
                         f"buffer of {args.cands_per_read} pairs per read, as bin/run_rl.sh:243 runs read_label; +8 B per pair in the byte count"}
-        if world == 1 and not args.no_e2e and len(read_lens) == 1:
+        if args.full and world == 1 and not args.no_e2e and len(read_lens) == 1:
             e2e_batch = min(args.launch_reads, 2_000_000)  # the streamed boundary in batches of 2 M reads (3 pinned slots of 300 MB)
             per_step = max(1, args.batch // e2e_batch)
             out["e2e_stream"] = e2e_stream(eng, reads, e2e_batch, args.steps * per_step, args.warmup * per_step, log)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             with tempfile.TemporaryDirectory() as td:
                 out["cpu_baseline"] = cpu_baseline(eng, reads, args.cpu_sample, k, td)
         print(json.dumps(out))

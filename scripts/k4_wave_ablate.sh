@@ -5,7 +5,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $ROOT
 for s in 30 31 32 33 0; do
-  LMAT_STOP_AFTER=$s python bench.py --steps 5 --warmup 2 --no-cpu --no-e2e --windows 0 2>/dev/null | python -c "
+  LMAT_STOP_AFTER=$s python bench.py --full --steps 5 --warmup 2 --no-cpu --no-e2e --windows 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 print('stop', $s, 'classify_ms %.3f' % d['roofline']['kernel_avg_ms'], 'value %.1f M' % (d['value'] / 1e6))"

@@ -1,10 +1,12 @@
 #!/bin/bash
-# kernel + memory-copy timeline of the boundary-inclusive bench leg (no counters): gpurun_out/trace_e2e/
+# kernel + memory-copy timeline of the boundary-inclusive bench leg (no counters): $OUT/trace_e2e/ (OUT defaults to prof_out/
+# in the repository)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${OUT:-$ROOT/prof_out}
 cd /tmp && export TMPDIR=/tmp
-rm -rf $ROOT/gpurun_out/trace_e2e
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $ROOT/gpurun_out/trace_e2e -o t -- python3 $ROOT/bench.py --no-cpu --steps 6 --warmup 1 > /dev/null 2>&1
-cd $ROOT/gpurun_out/trace_e2e && python3 - <<PY
+rm -rf $OUT/trace_e2e
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/trace_e2e -o t -- python3 $ROOT/bench.py --full --no-cpu --steps 6 --warmup 1 > /dev/null 2>&1
+cd $OUT/trace_e2e && python3 - <<PY
 import csv
 k=list(csv.DictReader(open("t_kernel_trace.csv")))
 m=list(csv.DictReader(open("t_memory_copy_trace.csv")))

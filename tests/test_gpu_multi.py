@@ -28,7 +28,7 @@ def _bench(tmp_path, name, *args, env=None):
     base = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     base.update(env or {})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--db-gb", "8.3", "--batch", "30000", "--launch-reads", "10000",
-                        "--steps", "2", "--warmup", "1", "--windows", "1", "--no-cpu", "--no-e2e", "--tally-out", out, *args],
+                        "--steps", "2", "--warmup", "1", "--full", "--windows", "1", "--no-cpu", "--no-e2e", "--tally-out", out, *args],
                        env=base, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
