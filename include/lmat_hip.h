@@ -342,6 +342,51 @@ int lmat_ingest_kmer_length(const lmat_ingest* ing);
 int lmat_ingest_lookup(const lmat_ingest* ing, uint64_t kmer, uint16_t* tids16, int cap);
 int lmat_db_from_ingest(lmat_ctx* ctx, lmat_ingest* ing, uint64_t table_bytes);
 
+/* ---- the database from genome FASTA (lmat_amd/csrc/dbgen.hip) ------------------------------------
+ * Replaces the reference's two offline CPU programs: kmerPrefixCounter (src/kmerPrefixCounter.cpp:114-147: genome FASTA ->
+ * canonical k-mers with the ids of the genomes that hold them) and tax_histo (src/tax_histo.cpp:210-284, TaxTree::getLcaMap
+ * src/kmerdb/TaxTree.hpp:160-260: per k-mer the owners the tree knows plus every node on their paths up to and including
+ * their lowest common ancestor).  The result is the tax_histo binary lmat_db_add_taxhisto reads, records in ascending k-mer
+ * order, every list in ASCENDING TAXID order (the reference writes unordered_map iteration order).
+ *   input    FASTA records headed ">" + decimal taxid; a sequence may span lines; records of one taxid are one owner.  Every
+ *            window of k consecutive ACGTacgt gives min(forward, reverse complement); any other byte breaks the run.
+ *   memory   everything on the device is sized by device_budget_bytes (0: half of the free memory); the k-mer space is cut into
+ *            2^prefix_bits passes by the top bits of the canonical k-mer (the reference's -l / -f), derived from the budget and
+ *            the base count unless given; the genome text is uploaded in chunks of chunk_bases (0: 16 Mi) with an overlap.
+ *   errors   a list of more than 65535 taxids is LMAT_E_CAPACITY (the reference truncates the 16-bit count silently); a pass
+ *            that does not fit a forced prefix_bits is LMAT_E_CAPACITY; nothing is ever cut short.
+ *   deviation: owners that are the root or a child of the root are treated like any other (the reference, built without
+ *            NDEBUG, asserts on them, TaxTree.hpp:204). */
+typedef struct lmat_build lmat_build;
+typedef struct {
+    uint64_t bases;               /* sequence bytes given                                                   */
+    uint64_t windows;             /* windows of k valid bases                                               */
+    uint64_t emitted_pairs;       /* (k-mer, owner) pairs the extraction emitted over all passes            */
+    uint64_t distinct_kmers;
+    uint64_t records_written;     /* distinct k-mers with at least one owner in the tree                    */
+    uint64_t dropped_unknown;     /* distinct k-mers none of whose owners is in the tree: no record         */
+    uint64_t singletons;          /* records whose list is one taxid                                        */
+    uint64_t total_list_entries;
+    uint64_t longest_list;
+    uint32_t passes;
+    uint32_t prefix_bits;
+    float extract_ms, sort_ms, segment_ms, closure_ms;   /* HIP-event time per stage, summed over the passes */
+} lmat_build_stats;
+int lmat_build_create(lmat_ctx* ctx, int k, const char* tree_fn, lmat_build** out);
+void lmat_build_destroy(lmat_build* b);
+const char* lmat_build_error(const lmat_build* b);
+int lmat_build_set_options(lmat_build* b, uint64_t device_budget_bytes, int prefix_bits /* -1: derive */, uint32_t chunk_bases /* 0: default */);
+int lmat_build_add_fasta(lmat_build* b, const char* fn);
+int lmat_build_add_sequence(lmat_build* b, uint32_t taxid, const uint8_t* ascii, uint64_t n);
+int lmat_build_run(lmat_build* b, lmat_build_stats* out);
+int lmat_build_write_taxhisto(lmat_build* b, const char* fn);
+/* Records [first, first + count) of the result: kmers[count], list_off[count + 1] (relative to the first record's list),
+ * tids[up to tid_cap] (LMAT_E_CAPACITY when the range holds more).  Any of the three may be NULL. */
+int lmat_build_fetch(lmat_build* b, uint64_t first, uint64_t count, uint64_t* kmers, uint64_t* list_off, uint32_t* tids, uint64_t tid_cap);
+/* The classify table straight from the result, without a file: needs a context with a taxonomy loaded; ends in the table
+ * lmat_db_begin / lmat_db_add_taxhisto / lmat_db_finalize build from the written file (the records go through the same parser). */
+int lmat_db_build_from_genomes(lmat_ctx* ctx, lmat_build* b, uint64_t table_bytes);
+
 /* ---- test hook: the decision step on given candidate tables ---------------------------------
  * Runs the decision kernels' own code -- std::sort(TCmp) (src/read_label.cpp:475-485, 892-893) and findReadLabelVer2
  * (:284-419) -- on n candidate tables given from outside instead of computed from reads: table i = the (32-bit taxid,

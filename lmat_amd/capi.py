@@ -27,6 +27,17 @@ class Params(C.Structure):
         return cls(1.0, 0.0, 0.0, 30, 1, prn_all, 1)
 
 
+class BuildStats(C.Structure):
+    """lmat_build_stats: what lmat_build_run counted and the HIP-event time of every stage."""
+    _fields_ = [("bases", C.c_uint64), ("windows", C.c_uint64), ("emitted_pairs", C.c_uint64), ("distinct_kmers", C.c_uint64),
+                ("records_written", C.c_uint64), ("dropped_unknown", C.c_uint64), ("singletons", C.c_uint64),
+                ("total_list_entries", C.c_uint64), ("longest_list", C.c_uint64), ("passes", C.c_uint32), ("prefix_bits", C.c_uint32),
+                ("extract_ms", C.c_float), ("sort_ms", C.c_float), ("segment_ms", C.c_float), ("closure_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 READ_RESULT_DTYPE = np.dtype([("status", "u1"), ("match_type", "u1"), ("cand_kmer_cnt", "<u2"), ("valid_kmers", "<i4"),
                               ("read_len", "<i4"), ("log_avg", "<f4"), ("stdev", "<f4"), ("call_tid", "<u4"),
                               ("call_score", "<f4"), ("cand_off", "<u4"), ("n_cand", "<u4"), ("bin_sel", "<i4")])
@@ -133,6 +144,16 @@ def load_library(path: str | None = None):
         "lmat_synth_read_windows": (i32, [vp, vp, u32, u64, u64, vp, vp, vp, u32, u32, P(u32), P(u32)]),
         "lmat_table_address": (i32, [i32, u64, u64, P(u64), P(u32), P(u32)]),
         "lmat_format_out": (C.c_int64, [vp, vp, u64, vp, vp, vp, i32, u64, vp, u64]),
+        "lmat_build_create": (i32, [vp, i32, cp, P(vp)]),
+        "lmat_build_destroy": (None, [vp]),
+        "lmat_build_error": (cp, [vp]),
+        "lmat_build_set_options": (i32, [vp, u64, i32, u32]),
+        "lmat_build_add_fasta": (i32, [vp, cp]),
+        "lmat_build_add_sequence": (i32, [vp, u32, vp, u64]),
+        "lmat_build_run": (i32, [vp, P(BuildStats)]),
+        "lmat_build_write_taxhisto": (i32, [vp, cp]),
+        "lmat_build_fetch": (i32, [vp, u64, u64, vp, vp, vp, u64]),
+        "lmat_db_build_from_genomes": (i32, [vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -155,7 +176,9 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_counts_reset", "lmat_counts_layout", "lmat_counts_device_ptr", "lmat_counts_get", "lmat_gather_bench",
             "lmat_table_address", "lmat_format_out", "lmat_stream_create", "lmat_stream_acquire", "lmat_stream_submit", "lmat_stream_submit_from", "lmat_host_alloc", "lmat_host_free",
             "lmat_stream_next", "lmat_stream_release", "lmat_stream_destroy", "lmat_counts_allreduce",
-            "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check"]
+            "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check",
+            "lmat_build_create", "lmat_build_destroy", "lmat_build_error", "lmat_build_set_options", "lmat_build_add_fasta", "lmat_build_add_sequence",
+            "lmat_build_run", "lmat_build_write_taxhisto", "lmat_build_fetch", "lmat_db_build_from_genomes"]
 
 
 def _ptr(a):
@@ -312,6 +335,55 @@ class Stream:
             self.h = None
 
 
+class Builder:
+    """lmat_build: genome FASTA + taxonomy tree -> k-mers with LCA-closed taxid lists, on the GPU of `eng`."""
+
+    def __init__(self, eng, k, tree):
+        self.eng, self.lib = eng, eng.lib
+        h = C.c_void_p()
+        eng._chk(self.lib.lmat_build_create(eng.ctx, k, tree.encode(), C.byref(h)))
+        self.h = h
+        self.stats = None
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise LmatError(rc, self.lib.lmat_build_error(self.h).decode(errors="replace"))
+
+    def set_options(self, budget_bytes=0, prefix_bits=-1, chunk_bases=0):
+        self._chk(self.lib.lmat_build_set_options(self.h, int(budget_bytes), int(prefix_bits), int(chunk_bases)))
+
+    def add_fasta(self, fn):
+        self._chk(self.lib.lmat_build_add_fasta(self.h, fn.encode()))
+
+    def add_sequence(self, taxid, seq):
+        bs = seq.encode() if isinstance(seq, str) else bytes(seq)
+        self._chk(self.lib.lmat_build_add_sequence(self.h, int(taxid), bs, len(bs)))
+
+    def run(self):
+        st = BuildStats()
+        self._chk(self.lib.lmat_build_run(self.h, C.byref(st)))
+        self.stats = st.as_dict()
+        return self.stats
+
+    def write_taxhisto(self, fn):
+        self._chk(self.lib.lmat_build_write_taxhisto(self.h, fn.encode()))
+
+    def fetch(self, first=0, count=None):
+        """-> (kmers uint64[count], list_off uint64[count + 1], tids uint32[list_off[-1]])"""
+        n = self.stats["records_written"] - first if count is None else count
+        km = np.zeros(n, dtype=np.uint64)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self.lib.lmat_build_fetch(self.h, first, n, _ptr(km), _ptr(off), None, 0))
+        td = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        self._chk(self.lib.lmat_build_fetch(self.h, first, n, None, None, _ptr(td), td.size))
+        return km, off, td[:int(off[-1])]
+
+    def close(self):
+        if self.h:
+            self.lib.lmat_build_destroy(self.h)
+            self.h = None
+
+
 class Engine:
     """One context on one GPU (lmat_ctx)."""
 
@@ -363,6 +435,38 @@ class Engine:
         if save_image:
             self._chk(self.lib.lmat_db_save_image(self.ctx, save_image.encode()))
         self._chk(self.lib.lmat_db_finalize(self.ctx))
+
+    # the database from genomes (lmat_build_*) ---------------------------------------
+    def _builder(self, fastas, tree, k, budget_bytes=0, prefix_bits=-1, chunk_bases=0):
+        b = Builder(self, k, tree)
+        try:
+            b.set_options(budget_bytes, prefix_bits, chunk_bases)
+            for f in ([fastas] if isinstance(fastas, str) else fastas):
+                b.add_fasta(f)
+            b.run()
+        except Exception:
+            b.close()
+            raise
+        return b
+
+    def build_taxhisto(self, fastas, tree, k, out, **opts):
+        """kmerPrefixCounter + tax_histo: genome FASTA file(s) ('>' + taxid headers) and a taxonomy tree -> the tax_histo
+        binary `out`.  opts: budget_bytes, prefix_bits, chunk_bases.  -> the build's statistics (dict)."""
+        b = self._builder(fastas, tree, k, **opts)
+        try:
+            b.write_taxhisto(out)
+            return b.stats
+        finally:
+            b.close()
+
+    def build_db_from_genomes(self, fastas, tree, k=20, table_bytes=0, **opts):
+        """The classify table straight from genome FASTA, no file in between (needs load_taxonomy first) -> statistics."""
+        b = self._builder(fastas, tree, k, **opts)
+        try:
+            self._chk(self.lib.lmat_db_build_from_genomes(self.ctx, b.h, int(table_bytes)))
+            return b.stats
+        finally:
+            b.close()
 
     def load_image(self, path, table_bytes=0):
         self._chk(self.lib.lmat_db_load_image(self.ctx, path.encode(), table_bytes))

@@ -208,6 +208,11 @@ void Ingest::push(uint64_t kmer, const std::vector<uint16_t>& lst) {
 bool Ingest::add_taxhisto(const char* fn) {
     FILE* in = fopen(fn, "rb");
     if (!in) { err = std::string("Error: unable to open kmer db [") + fn + "]"; return false; }
+    return add_taxhisto_stream(in, fn);
+}
+
+bool Ingest::add_taxhisto_stream(FILE* in, const char* fn) {
+    (void)fn;
     fseek(in, 0, SEEK_END);
     const long fsz = ftell(in);
     fseek(in, 0, SEEK_SET);

@@ -68,6 +68,8 @@ struct Ingest {
     bool idmap_from_tree(const char* tree_fn);
     bool set_options(int cutoff, const char* species_map_fn, const char* human_fn, const char* adaptor_fn, uint32_t adaptor);
     bool add_taxhisto(const char* fn);
+    // the same records from an open seekable stream (a file, or the in-memory stream of lmat_db_build_from_genomes); closes it
+    bool add_taxhisto_stream(FILE* in, const char* fn);
     bool save_image(const char* fn) const;
     bool load_image(const char* fn);
     // image -> flush callback in chunks of flush_every k-mers (lists are read first); nothing is kept in memory

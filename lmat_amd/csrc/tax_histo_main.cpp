@@ -1,0 +1,93 @@
+// build_tax_histo -- genome FASTA + taxonomy tree -> the tax_histo binary read_label -d / make_db_image ingest, on the GPU.
+// One tool for the reference's kmerPrefixCounter (src/kmerPrefixCounter.cpp) + tax_histo (src/tax_histo.cpp) pair; the
+// closing stdout lines keep tax_histo's wording (tax_histo.cpp:297-313).
+#include <unistd.h>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <string>
+#include <vector>
+#include "../../include/lmat_hip.h"
+
+static void usage() {
+    fprintf(stderr,
+            "Usage:\n"
+            " -i <string>  - input fasta_fn (headers: '>' + decimal taxid), or with -l a file that lists fasta files\n"
+            " -l           - -i names a list of fasta files, one per line\n"
+            " -k <int>     - kmer length (1..20)\n"
+            " -t <string>  - tax tree data file\n"
+            " -o <string>  - output filename\n"
+            " -b <float>   - device memory budget in GiB; optional; default: half of the free memory\n"
+            " -p <int>     - prefix bits: the k-mer space is built in 2^p passes; optional; default: derived from the budget\n"
+            " -V           - print version and exit\n"
+            " -h           - print help and exit\n\n");
+}
+
+int main(int argc, char* argv[]) {
+    printf("invocation: ");
+    for (int j = 0; j < argc; j++) printf("%s ", argv[j]);
+    printf("\n");
+    std::string input_fn, tree_fn, out_fn;
+    int k = 0, prefix_bits = -1;
+    bool is_list = false;
+    double budget_gib = 0;
+    int c;
+    while ((c = getopt(argc, argv, "i:lk:t:o:b:p:Vh")) != -1) {
+        switch (c) {
+            case 'i': input_fn = optarg; break;
+            case 'l': is_list = true; break;
+            case 'k': k = atoi(optarg); break;
+            case 't': tree_fn = optarg; break;
+            case 'o': out_fn = optarg; break;
+            case 'b': budget_gib = atof(optarg); break;
+            case 'p': prefix_bits = atoi(optarg); break;
+            case 'V': printf("build_tax_histo (lmat_hip) 1\n"); return 0;
+            default: usage(); return c == 'h' ? 0 : 255;
+        }
+    }
+    if (input_fn.empty() || tree_fn.empty() || out_fn.empty() || k == 0) { usage(); return 255; }
+    std::vector<std::string> fastas;
+    if (is_list) {
+        std::ifstream in(input_fn);
+        if (!in) { fprintf(stderr, "failed to open %s for reading\n", input_fn.c_str()); return 1; }
+        std::string line;
+        while (std::getline(in, line)) if (!line.empty()) fastas.push_back(line);
+    } else fastas.push_back(input_fn);
+
+    lmat_ctx* ctx = nullptr;
+    if (lmat_ctx_create(0, nullptr, &ctx) != LMAT_OK) { fprintf(stderr, "ERROR! no usable HIP device (the engine has no CPU path)\n"); return 1; }
+    printf("info: starting tax tree load from filename: %s\n", tree_fn.c_str());
+    lmat_build* b = nullptr;
+    int rc = lmat_build_create(ctx, k, tree_fn.c_str(), &b);
+    if (rc != LMAT_OK) { fprintf(stderr, "ERROR! %s\n", lmat_last_error(ctx)); lmat_ctx_destroy(ctx); return 1; }
+    auto fail = [&](const char* what) {
+        fprintf(stderr, "ERROR! %s: %s\n", what, lmat_build_error(b));
+        lmat_build_destroy(b);
+        lmat_ctx_destroy(ctx);
+        return 1;
+    };
+    if (lmat_build_set_options(b, (uint64_t)(budget_gib * 1073741824.0), prefix_bits, 0) != LMAT_OK) return fail("options");
+    for (auto& fn : fastas) {
+        printf("opening: %s\n", fn.c_str());
+        if (lmat_build_add_fasta(b, fn.c_str()) != LMAT_OK) return fail("input");
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    lmat_build_stats s;
+    if (lmat_build_run(b, &s) != LMAT_OK) return fail("build");
+    const double tm = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stderr, "opening for writing: %s\n", out_fn.c_str());
+    if (lmat_build_write_taxhisto(b, out_fn.c_str()) != LMAT_OK) return fail("output");
+    printf("bases: %llu windows: %llu distinct kmers: %llu passes: %u\n", (unsigned long long)s.bases, (unsigned long long)s.windows,
+           (unsigned long long)s.distinct_kmers, s.passes);
+    printf("kernel ms: extract %.3f sort %.3f segment %.3f closure %.3f\n", s.extract_ms, s.sort_ms, s.segment_ms, s.closure_ms);
+    printf("longest list: %llu\n", (unsigned long long)s.longest_list);
+    printf("total taxids: %llu\nrem kmer cnt: %llu\n", (unsigned long long)s.total_list_entries, (unsigned long long)s.dropped_unknown);
+    printf("singletons: %llu\n", (unsigned long long)s.singletons);
+    printf("\ntotal annotate time: %g\n", tm);
+    printf("num mapping kmers processed: %llu\n", (unsigned long long)s.records_written);
+    printf("kmers per second (not counting startup time): %g\n", tm > 0 ? (double)s.distinct_kmers / tm : 0.0);
+    lmat_build_destroy(b);
+    lmat_ctx_destroy(ctx);
+    return 0;
+}

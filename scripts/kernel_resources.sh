@@ -1,9 +1,10 @@
 #!/bin/bash
-# Registers, scratch and LDS of every kernel in kernels.o (from the code object's metadata): spills in a classify class show here first.
+# Registers, scratch and LDS of every kernel in kernels.o -- or in the object named as first argument, e.g. dbgen.o -- (from the code
+# object's metadata): spills in a classify class show here first.
 set -e
 cd "$(dirname "$0")/../lmat_amd/csrc"
 T=$(mktemp -d)
-objcopy --dump-section .hip_fatbin=$T/fat.bin kernels.o
+objcopy --dump-section .hip_fatbin=$T/fat.bin "${1:-kernels.o}"
 /opt/rocm/lib/llvm/bin/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/fat.bin --output=$T/dev.co --unbundle
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes $T/dev.co | python3 -c '
 import sys,re
