@@ -387,6 +387,48 @@ int lmat_build_fetch(lmat_build* b, uint64_t first, uint64_t count, uint64_t* km
  * lmat_db_begin / lmat_db_add_taxhisto / lmat_db_finalize build from the written file (the records go through the same parser). */
 int lmat_db_build_from_genomes(lmat_ctx* ctx, lmat_build* b, uint64_t table_bytes);
 
+/* ---- adding genomes to an existing database: tax_histo files as further inputs of a build ----
+ * lmat_build_add_taxhisto (any number, before lmat_build_run) makes an existing tax_histo file an input beside, or instead of,
+ * sequence.  lmat_build_run then produces the merge of the files and -- if any sequence was added -- of what the genomes alone
+ * would give; records in ascending k-mer order, lists in ascending taxid order, through lmat_build_write_taxhisto,
+ * lmat_build_fetch and lmat_db_build_from_genomes as before.  Per k-mer, with X the union of the entries of every source
+ * that holds it:
+ *   one source                  its list, ascending.  The list is COPIED, NOT RE-CLOSED: inputs are taken to be closed lists, as
+ *                               tax_histo and this builder write them
+ *   several sources, |X| = 1    that taxid
+ *   otherwise                   X plus every node on the path from each source's shallowest entry up to and including the LCA
+ *                               of those shallowest entries, every taxid once (for closed lists this is the closure of the
+ *                               union of the original owners; the engine computes it as the closure of X taken as owners)
+ * Lists of an input may be in any order and of any length the format holds; the output bytes do not depend on prefix_bits, the
+ * budget or the order in which inputs were added.  The merge runs inside the prefix passes: a pass takes the contiguous slice
+ * of every input with its prefix; device_budget_bytes bounds it and the derived prefix_bits accounts for the inputs' record and
+ * entry counts (72 bytes per record, 12 per entry of the largest slice); a forced prefix_bits that does not fit is
+ * LMAT_E_CAPACITY.  The files themselves are parsed when they are added and held on the host until the builder is destroyed.
+ *   errors   (the message names the file)  header k differs from the builder's: LMAT_E_ARG.  Malformed or truncated file, bad
+ *            sanity word, k-mer wider than 2k bits, k-mers not strictly ascending, bytes behind the last record, A TAXID
+ *            REPEATED INSIDE ONE LIST: LMAT_E_IO.  A taxid the builder's tree does not know: LMAT_E_TAXONOMY, naming it.  A
+ *            merged list of more than 65535 entries: LMAT_E_CAPACITY (from lmat_build_run).  A record with an empty list
+ *            carries nothing and is skipped.  A file that fails is not added; the builder stays usable.
+ *   stats    lmat_build_stats keeps its layout: with tax_histo inputs records_written, singletons, total_list_entries and
+ *            longest_list describe the final result, bases / windows / emitted_pairs / distinct_kmers / dropped_unknown the
+ *            genome part only; without inputs every field is what it was. */
+typedef struct {
+    uint32_t inputs;               /* tax_histo files added                                                     */
+    uint32_t passes;
+    uint64_t records_in;           /* records with a list, over all files                                       */
+    uint64_t entries_in;           /* their list entries                                                        */
+    uint64_t records_one_source;   /* result records whose k-mer one source held (a file, or the genomes)       */
+    uint64_t records_merged;       /* ... two or more sources held                                              */
+    uint64_t records_grown;        /* merged records whose list holds a node that no source list held           */
+    float upload_ms, sort_ms, segment_ms, union_ms, histogram_ms;   /* HIP-event time per merge stage, summed over the passes */
+} lmat_merge_stats;
+int lmat_build_add_taxhisto(lmat_build* b, const char* fn);
+int lmat_build_merge_stats(const lmat_build* b, lmat_merge_stats* out);   /* after lmat_build_run; all zero without tax_histo inputs */
+/* After lmat_build_run, with or without tax_histo inputs: for every taxid that occurs, the number of result records whose list
+ * holds it, ascending by taxid (the map of the reference's countTaxidFrequency, src/countTaxidFrequency.cpp:105-139), counted
+ * on the device.  *n is the number of such taxids, set even when cap is too small (LMAT_E_CAPACITY): a cap of 0 asks for it. */
+int lmat_build_taxid_counts(lmat_build* b, uint32_t* tids, uint64_t* counts, uint64_t cap, uint64_t* n);
+
 /* ---- test hook: the decision step on given candidate tables ---------------------------------
  * Runs the decision kernels' own code -- std::sort(TCmp) (src/read_label.cpp:475-485, 892-893) and findReadLabelVer2
  * (:284-419) -- on n candidate tables given from outside instead of computed from reads: table i = the (32-bit taxid,

@@ -38,6 +38,16 @@ class BuildStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MergeStats(C.Structure):
+    """lmat_merge_stats: what the merge of tax_histo inputs counted and the HIP-event time of its stages."""
+    _fields_ = [("inputs", C.c_uint32), ("passes", C.c_uint32), ("records_in", C.c_uint64), ("entries_in", C.c_uint64),
+                ("records_one_source", C.c_uint64), ("records_merged", C.c_uint64), ("records_grown", C.c_uint64),
+                ("upload_ms", C.c_float), ("sort_ms", C.c_float), ("segment_ms", C.c_float), ("union_ms", C.c_float), ("histogram_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 READ_RESULT_DTYPE = np.dtype([("status", "u1"), ("match_type", "u1"), ("cand_kmer_cnt", "<u2"), ("valid_kmers", "<i4"),
                               ("read_len", "<i4"), ("log_avg", "<f4"), ("stdev", "<f4"), ("call_tid", "<u4"),
                               ("call_score", "<f4"), ("cand_off", "<u4"), ("n_cand", "<u4"), ("bin_sel", "<i4")])
@@ -154,6 +164,9 @@ def load_library(path: str | None = None):
         "lmat_build_write_taxhisto": (i32, [vp, cp]),
         "lmat_build_fetch": (i32, [vp, u64, u64, vp, vp, vp, u64]),
         "lmat_db_build_from_genomes": (i32, [vp, vp, u64]),
+        "lmat_build_add_taxhisto": (i32, [vp, cp]),
+        "lmat_build_merge_stats": (i32, [vp, P(MergeStats)]),
+        "lmat_build_taxid_counts": (i32, [vp, vp, vp, u64, P(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -178,7 +191,8 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_stream_next", "lmat_stream_release", "lmat_stream_destroy", "lmat_counts_allreduce",
             "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check",
             "lmat_build_create", "lmat_build_destroy", "lmat_build_error", "lmat_build_set_options", "lmat_build_add_fasta", "lmat_build_add_sequence",
-            "lmat_build_run", "lmat_build_write_taxhisto", "lmat_build_fetch", "lmat_db_build_from_genomes"]
+            "lmat_build_run", "lmat_build_write_taxhisto", "lmat_build_fetch", "lmat_db_build_from_genomes",
+            "lmat_build_add_taxhisto", "lmat_build_merge_stats", "lmat_build_taxid_counts"]
 
 
 def _ptr(a):
@@ -359,11 +373,33 @@ class Builder:
         bs = seq.encode() if isinstance(seq, str) else bytes(seq)
         self._chk(self.lib.lmat_build_add_sequence(self.h, int(taxid), bs, len(bs)))
 
+    def add_taxhisto(self, fn):
+        """An existing tax_histo file as a further input: run() gives the merge (lmat_build_add_taxhisto)."""
+        self._chk(self.lib.lmat_build_add_taxhisto(self.h, fn.encode()))
+
     def run(self):
         st = BuildStats()
         self._chk(self.lib.lmat_build_run(self.h, C.byref(st)))
         self.stats = st.as_dict()
         return self.stats
+
+    @property
+    def merge_stats(self):
+        """lmat_merge_stats of the last run (dict)."""
+        ms = MergeStats()
+        self._chk(self.lib.lmat_build_merge_stats(self.h, C.byref(ms)))
+        return ms.as_dict()
+
+    def taxid_counts(self):
+        """-> (taxids uint32[n] ascending, counts uint64[n]): result records whose list holds each taxid."""
+        n = C.c_uint64(0)
+        rc = self.lib.lmat_build_taxid_counts(self.h, None, None, 0, C.byref(n))
+        if rc != 0 and n.value == 0:
+            self._chk(rc)
+        tids = np.zeros(max(n.value, 1), dtype=np.uint32)
+        cnts = np.zeros(max(n.value, 1), dtype=np.uint64)
+        self._chk(self.lib.lmat_build_taxid_counts(self.h, _ptr(tids), _ptr(cnts), n.value, C.byref(n)))
+        return tids[:n.value], cnts[:n.value]
 
     def write_taxhisto(self, fn):
         self._chk(self.lib.lmat_build_write_taxhisto(self.h, fn.encode()))
@@ -437,12 +473,14 @@ class Engine:
         self._chk(self.lib.lmat_db_finalize(self.ctx))
 
     # the database from genomes (lmat_build_*) ---------------------------------------
-    def _builder(self, fastas, tree, k, budget_bytes=0, prefix_bits=-1, chunk_bases=0):
+    def _builder(self, fastas, tree, k, budget_bytes=0, prefix_bits=-1, chunk_bases=0, taxhistos=()):
         b = Builder(self, k, tree)
         try:
             b.set_options(budget_bytes, prefix_bits, chunk_bases)
-            for f in ([fastas] if isinstance(fastas, str) else fastas):
+            for f in ([fastas] if isinstance(fastas, str) else fastas or ()):
                 b.add_fasta(f)
+            for f in ([taxhistos] if isinstance(taxhistos, str) else taxhistos):
+                b.add_taxhisto(f)
             b.run()
         except Exception:
             b.close()
@@ -456,6 +494,17 @@ class Engine:
         try:
             b.write_taxhisto(out)
             return b.stats
+        finally:
+            b.close()
+
+    def merge_taxhisto(self, inputs, tree, k, out, fasta=None, **opts):
+        """Existing tax_histo file(s) `inputs`, merged with each other and -- with `fasta` -- with the genomes of those FASTA
+        file(s), into the tax_histo binary `out`: adding genomes to a database.  opts as build_taxhisto.
+        -> the build's statistics (dict) with the merge's under "merge"."""
+        b = self._builder(fasta, tree, k, taxhistos=inputs, **opts)
+        try:
+            b.write_taxhisto(out)
+            return {**b.stats, "merge": b.merge_stats}
         finally:
             b.close()
 

@@ -14,6 +14,14 @@
 // others), so the owners of one k-mer arrive in tour order and the closure needs no de-duplication: the first owner walks up
 // to and including the LCA of the first and the last, every later owner walks up to -- not including -- its LCA with the owner
 // before it; those pieces are disjoint and their union is the closure (the "virtual tree" of the owners).
+//
+// Existing tax_histo files as further inputs (lmat_build_add_taxhisto): inside the same prefix passes the slice
+// of every input with the pass's prefix and the pass's own result from the genomes are merged per k-mer:
+//   one key per input RECORD (k-mer << source bits | source), rocPRIM radix sort, mseg_flag / mseg_scatter (runs of one k-mer),
+//   union_classify (one-source runs are sized, gathered sets beyond 64 entries get a side-buffer segment, sorted by segment),
+//   union_kernel<count>, exclusive scan, union_kernel<write>: a one-source list is copied, the others are the closure of the union
+//   of the stored entries taken as owners -- the same virtual-tree walk over the entries in Euler-tour order, equal neighbours dropped.
+// hist_kernel counts, for either kind of run, the result records whose list holds each taxid (countTaxidFrequency's map).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -359,6 +367,287 @@ __global__ __launch_bounds__(256) void long_copy_kernel(const u32* sorted, const
     for (u32 i = threadIdx.x; i < n; i += blockDim.x) dst[i] = sorted[b + i];
 }
 
+// ---------------------------------------------------------------------------------------------- merge of tax_histo inputs
+// counters of the union, behind the C_* words of the same array
+enum { M_EMPTY = C_N, M_ONE, M_MERGED, M_GROWN, M_BIG_RUNS, M_BIG_ENTRIES, M_TOTAL };
+constexpr u32 kSmall = 0xFFFFFFFFu;   // aux of a run with several sources whose gathered entries fit the wave
+
+__global__ __launch_bounds__(256) void iota_kernel(u32* v, u32 n) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = i;
+}
+
+// index of taxid t in the ascending node_tid (every taxid that gets here is a node of the tree)
+__device__ __forceinline__ u32 node_of_tid(const u32* node_tid, u32 n_nodes, u32 t) {
+    u32 lo = 0, hi = n_nodes;
+    while (hi - lo > 1) { const u32 m = (lo + hi) >> 1; if (node_tid[m] <= t) lo = m; else hi = m; }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void tid_to_node_kernel(const u32* tids, u64 n, const u32* node_tid, u32 n_nodes, u32* out) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = node_of_tid(node_tid, n_nodes, tids[i]);
+}
+
+// The pass's result from the genomes as one more source: record rec_base + r, entries from ent_base on.  A run without a known owner has
+// no list: its key gets the bit above the k-mer, the sort puts it behind all others and the host cuts them off.
+__global__ __launch_bounds__(256) void genome_source_kernel(u32 R, const u64* g_kmer, const u64* g_off, u32 rec_base, u32 ent_base, u32 src, int src_bits,
+                                                             int key_bits, u64* keys, u32* rec_off, u64* counters) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    bool empty = false;
+    if (r < R) {
+        const u64 e = g_off[r + 1];
+        empty = e == g_off[r];
+        keys[rec_base + r] = (g_kmer[r] << src_bits) | src | (empty ? 1ull << key_bits : 0ull);
+        rec_off[rec_base + r + 1] = ent_base + (u32)e;
+    }
+    const u32 n = __popcll(__ballot(empty));
+    if (n && lane_id() == 0) atomicAdd(&counters[M_EMPTY], (u64)n);
+}
+
+__global__ __launch_bounds__(256) void mseg_flag_kernel(const u64* keys, u32 n, int src_bits, u32* flag) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) flag[i] = (i == 0 || (keys[i] >> src_bits) != (keys[i - 1] >> src_bits)) ? 1u : 0u;
+}
+
+// pos = exclusive scan of flag; run_start[r] = first sorted record of run r, run_start[R] = n
+__global__ __launch_bounds__(256) void mseg_scatter_kernel(const u32* flag, const u32* pos, u32 n, u32* run_start, u64* totals) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (flag[i]) run_start[pos[i]] = i;
+    if (i == n - 1) {
+        const u32 R = pos[i] + flag[i];
+        run_start[R] = n;
+        totals[0] = R;
+    }
+}
+
+__global__ __launch_bounds__(256) void mrun_kmer_kernel(const u64* keys, const u32* run_start, u32 R, int src_bits, u64 kmask, u64* out) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < R) out[r] = (keys[run_start[r]] >> src_bits) & kmask;
+}
+
+struct UnionArgs {
+    u32 R;
+    const u32* run_start;    // [R + 1] into rec
+    const u32* rec;          // sorted: index of the record in rec_off
+    const u32* rec_off;      // [records + 1] into ent
+    const u32* ent;          // dense node index of every stored entry
+    const u32* tin;          // [n_nodes] Euler-tour entry time of the node
+    const u32* node_at;      // [n_nodes] its inverse
+    const u32* parent;
+    const u32* depth;
+    const u32* node_tid;
+    u32* aux;                // [R] runs with several sources: kSmall, or the slot of the side-buffer segment
+    u32* big_run;            // [slots]
+    u32* big_begin;          // [slots] segment of the gathered tour indices
+    u32* big_end;
+    const u32* big_sorted;
+    u64* cnt;                // [R]
+    const u64* off;          // write pass: [R + 1]
+    u32* tids;
+    u32* long_tmp;
+    u32* long_begin;
+    u32* long_end;
+    u32* long_run;
+    u64* counters;
+};
+
+template <class T> __device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// One run per lane.  A run with one source has its list's length (a copy follows); a run with several gets kSmall when the entries of all its
+// lists together fit the 64 lanes, else a segment of the side buffer, filled by big_gather_kernel and ordered by rocPRIM's segmented sort.
+__global__ __launch_bounds__(256) void union_classify_kernel(UnionArgs a) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = r < a.R;
+    u32 ns = 0, G = 0;
+    if (active) {
+        const u32 s = a.run_start[r], e = a.run_start[r + 1];
+        ns = e - s;
+        for (u32 i = s; i < e; ++i) { const u32 q = a.rec[i]; G += a.rec_off[q + 1] - a.rec_off[q]; }
+    }
+    const bool one = active && ns == 1;
+    if (one) a.cnt[r] = G;
+    if (active && ns > 1) {
+        u32 slot = kSmall;
+        if (G > 64) {
+            slot = (u32)atomicAdd(&a.counters[M_BIG_RUNS], 1ull);
+            const u32 at = (u32)atomicAdd(&a.counters[M_BIG_ENTRIES], (u64)G);
+            a.big_run[slot] = r;
+            a.big_begin[slot] = at;
+            a.big_end[slot] = at + G;
+        }
+        a.aux[r] = slot;
+    }
+    const u32 n_one = __popcll(__ballot(one)), n_multi = __popcll(__ballot(active && ns > 1)), n_single = __popcll(__ballot(one && G == 1));
+    const u32 n_long = __popcll(__ballot(one && G > 64));
+    const u64 entries = wave_sum<u64>(one ? G : 0), long_entries = wave_sum<u64>(one && G > 64 ? G : 0);
+    u32 longest = one ? G : 0;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) longest = max(longest, (u32)__shfl_xor(longest, d));
+    if (lane_id() == 0) {
+        if (n_one) { atomicAdd(&a.counters[M_ONE], (u64)n_one); atomicAdd(&a.counters[C_ENTRIES], entries); atomicMax(&a.counters[C_LONGEST], (u64)longest); }
+        if (n_multi) atomicAdd(&a.counters[M_MERGED], (u64)n_multi);
+        if (n_single) atomicAdd(&a.counters[C_SINGLETONS], (u64)n_single);
+        if (n_long) { atomicAdd(&a.counters[C_LONG_RUNS], (u64)n_long); atomicAdd(&a.counters[C_LONG_ENTRIES], long_entries); }
+    }
+}
+
+// one block per side-buffer segment: the tour index of every entry of every list of the run
+__global__ __launch_bounds__(256) void big_gather_kernel(UnionArgs a, u32* big_tmp) {
+    const u32 q = blockIdx.x, r = a.big_run[q];
+    u32 at = a.big_begin[q];
+    for (u32 i = a.run_start[r]; i < a.run_start[r + 1]; ++i) {
+        const u32 rc = a.rec[i], b0 = a.rec_off[rc], n = a.rec_off[rc + 1] - b0;
+        for (u32 t = threadIdx.x; t < n; t += blockDim.x) big_tmp[at + t] = a.tin[a.ent[b0 + t]];
+        at += n;
+    }
+}
+
+// One run per lane.  One source: the list is copied -- by the lane while it ascends (a list this builder wrote), else by the wave, ranked; beyond
+// 64 entries through the side buffer of the long lists.  Several sources: the wave orders the entries of all lists by tour index (in LDS, or
+// the segment sorted beforehand), equal neighbours are one entry, and the walk of closure_kernel gives the closure in disjoint pieces.
+template <bool WRITE>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void union_kernel(UnionArgs a) {
+    __shared__ u32 s_stage[kWavesPerBlock][64];   // gathered tour indices, later the list to be ranked
+    __shared__ u32 s_seq[kWavesPerBlock][64];     // tour indices in order
+    const u32 lane = lane_id();
+    const u32 wv = threadIdx.x >> 6;
+    const u64 r64 = ((u64)blockIdx.x * kWavesPerBlock + wv) * 64 + lane;
+    const bool active = r64 < a.R;
+    const u32 r = active ? (u32)r64 : 0;
+    u32 s = 0, e = 0;
+    bool wave_job = false;
+    if (active) {
+        s = a.run_start[r];
+        e = a.run_start[r + 1];
+        if (e - s > 1) wave_job = true;
+        else if (WRITE) {
+            const u32 q = a.rec[s], b0 = a.rec_off[q], n = a.rec_off[q + 1] - b0;
+            if (n > 64) wave_job = true;
+            else {
+                u32* dst = a.tids + a.off[r];
+                u32 prev = 0;
+                for (u32 i = 0; i < n; ++i) {
+                    const u32 x = a.ent[b0 + i];
+                    if (i && x <= prev) { wave_job = true; break; }
+                    dst[i] = a.node_tid[x];
+                    prev = x;
+                }
+            }
+        }
+    }
+    u64 jobs = __ballot(wave_job);
+    while (jobs) {
+        const int b = __ffsll((long long)jobs) - 1;
+        jobs &= jobs - 1;
+        const u32 rs = __shfl(s, b), re = __shfl(e, b), rr = __shfl(r, b);
+        u32 n = 0;
+        bool is_long = false;
+        u32 long_at = 0;
+        u32* dst = &s_stage[wv][0];
+        if (WRITE) {
+            n = (u32)(a.off[rr + 1] - a.off[rr]);
+            is_long = n > 64;
+            if (is_long) {
+                if (lane == 0) {
+                    const u32 slot = (u32)atomicAdd(&a.counters[C_LONG_RUNS], 1ull);
+                    long_at = (u32)atomicAdd(&a.counters[C_LONG_ENTRIES], (u64)n);
+                    a.long_begin[slot] = long_at;
+                    a.long_end[slot] = long_at + n;
+                    a.long_run[slot] = rr;
+                }
+                long_at = __shfl(long_at, 0);
+                dst = a.long_tmp + long_at;
+            }
+        }
+        if (re - rs == 1) {   // write pass only: the copy of a list that does not ascend or is long
+            const u32 q = a.rec[rs], b0 = a.rec_off[q];
+            for (u32 i = lane; i < n; i += 64) dst[i] = a.node_tid[a.ent[b0 + i]];
+        } else {
+            const u32 slot = a.aux[rr];
+            const u32* seq;
+            u32 G;
+            if (slot == kSmall) {
+                G = 0;
+                for (u32 i = rs; i < re; ++i) {
+                    const u32 q = a.rec[i], b0 = a.rec_off[q], m = a.rec_off[q + 1] - b0;
+                    if (lane < m) s_stage[wv][G + lane] = a.tin[a.ent[b0 + lane]];   // G + m <= 64: union_classify summed the same lengths
+                    G += m;
+                }
+                wave_sync();
+                const u32 v = lane < G ? s_stage[wv][lane] : 0xFFFFFFFFu;
+                u32 rank = 0;
+                for (u32 t = 0; t < G; ++t) { const u32 o = s_stage[wv][t]; rank += (o < v || (o == v && t < lane)) ? 1u : 0u; }
+                wave_sync();   // the stage is free for the list from here on
+                if (lane < G) s_seq[wv][rank] = v;
+                wave_sync();
+                seq = &s_seq[wv][0];
+            } else {
+                seq = a.big_sorted + a.big_begin[slot];
+                G = a.big_end[slot] - a.big_begin[slot];
+            }
+            const u32 top = lca2(a.parent, a.depth, a.node_at[seq[0]], a.node_at[seq[G - 1]]);
+            u32 total = 0, distinct = 0;
+            for (u32 base = 0; base < G; base += 64) {
+                const u32 j = base + lane;
+                u32 node = 0, len = 0;
+                bool fresh = false;
+                if (j < G) {
+                    const u32 t = seq[j];
+                    node = a.node_at[t];
+                    if (j == 0) { len = a.depth[node] - a.depth[top] + 1; fresh = true; }
+                    else {
+                        const u32 tp = seq[j - 1];
+                        fresh = tp != t;
+                        if (fresh) len = a.depth[node] - a.depth[lca2(a.parent, a.depth, a.node_at[tp], node)];
+                    }
+                }
+                u32 incl = len;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const u32 o = __shfl_up(incl, d);
+                    if ((int)lane >= d) incl += o;
+                }
+                if (WRITE) {
+                    u32 at = total + incl - len;
+                    for (u32 x = node, i = 0; i < len; ++i, x = a.parent[x]) dst[at++] = a.node_tid[x];
+                }
+                total += __shfl(incl, 63);
+                distinct += __popcll(__ballot(fresh));
+            }
+            if (!WRITE && lane == 0) {
+                a.cnt[rr] = total;
+                atomicAdd(&a.counters[C_ENTRIES], (u64)total);
+                atomicMax(&a.counters[C_LONGEST], (u64)total);
+                if (total == 1) atomicAdd(&a.counters[C_SINGLETONS], 1ull);
+                if (total > distinct) atomicAdd(&a.counters[M_GROWN], 1ull);
+                if (total > kMaxList) atomicMax(&a.counters[C_TOOLONG], (u64)total);
+                if (total > 64) { atomicAdd(&a.counters[C_LONG_RUNS], 1ull); atomicAdd(&a.counters[C_LONG_ENTRIES], (u64)total); }
+            }
+        }
+        if (WRITE && !is_long) {
+            // ascending order within the wave: the entries are distinct, the rank of one is the number of smaller ones
+            wave_sync();
+            const u32 v = lane < n ? s_stage[wv][lane] : 0xFFFFFFFFu;
+            u32 rank = 0;
+            for (u32 t = 0; t < n; ++t) rank += s_stage[wv][t] < v ? 1u : 0u;
+            if (lane < n) a.tids[a.off[rr] + rank] = v;
+            wave_sync();
+        }
+    }
+}
+
+// hist[node] += 1 for every entry of the final lists: the number of records whose list holds the taxid
+__global__ __launch_bounds__(256) void hist_kernel(const u32* tids, u64 n, const u32* node_tid, u32 n_nodes, u64* hist) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) atomicAdd(&hist[node_of_tid(node_tid, n_nodes, tids[i])], 1ull);
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host
 struct DevBuf {
     void* p = nullptr;
@@ -398,6 +687,16 @@ struct lmat_build {
     std::vector<u64> list_off;           // [records + 1]
     std::vector<u32> tids;
     lmat_build_stats stats;
+    // tax_histo files to be merged in (lmat_build_add_taxhisto): parsed when added, lists as dense node indices in file order
+    struct Input {
+        std::string fn;
+        std::vector<u64> kmers;          // strictly ascending
+        std::vector<u64> off;            // [records + 1]
+        std::vector<u32> nodes;
+    };
+    std::vector<Input> inputs;
+    lmat_merge_stats mstats;
+    std::vector<u64> node_counts;        // [n_nodes] result records whose list holds the node
 };
 
 namespace {
@@ -486,6 +785,75 @@ void add_record(lmat_build* b, u32 taxid) {
 
 int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry);
 
+// KmerFileMetaData.cpp:16-31 + tax_histo.cpp:250-266, as dbbuild.cpp reads it -- but strict: the header's count of records must be there
+int parse_taxhisto(lmat_build* b, const char* fn, lmat_build::Input& in) {
+    const std::string name(fn);
+    FILE* f = fopen(fn, "rb");
+    if (!f) return berr(b, LMAT_E_IO, "failed to open " + name + " for reading");
+    std::vector<uint8_t> buf;
+    fseek(f, 0, SEEK_END);
+    const long fsz = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    if (fsz > 0) buf.resize((size_t)fsz);
+    const bool rd = fsz >= 0 && (buf.empty() || fread(buf.data(), 1, buf.size(), f) == buf.size());
+    fclose(f);
+    if (!rd) return berr(b, LMAT_E_IO, "read error on " + name);
+    if (buf.size() < 29) return berr(b, LMAT_E_IO, name + ": truncated tax_histo header");
+    uint32_t version, klen;
+    uint64_t count, test;
+    memcpy(&count, &buf[4], 8);
+    memcpy(&test, &buf[12], 8);
+    memcpy(&version, &buf[20], 4);
+    memcpy(&klen, &buf[25], 4);
+    if (test != ~0ull) return berr(b, LMAT_E_IO, name + ": kmer data file is invalid; should have read 64 1s, but didn't");
+    if (version != 999 || buf[24] != 'N') return berr(b, LMAT_E_IO, name + ": not a tax_histo file (version/location flag)");
+    if ((int)klen != b->k) return berr(b, LMAT_E_ARG, name + ": k-mer length " + std::to_string(klen) + " of the file differs from the builder's " + std::to_string(b->k));
+    in.fn = name;
+    in.off.assign(1, 0);
+    size_t pos = 29;
+    const size_t end = buf.size();
+    std::vector<u32> chk;
+    u64 prev = 0;
+    for (u64 i = 0; i < count; ++i) {
+        if (end - pos < 10) return berr(b, LMAT_E_IO, name + ": truncated tax_histo record " + std::to_string(i) + " of " + std::to_string(count));
+        u64 km;
+        uint16_t n;
+        memcpy(&km, &buf[pos], 8);
+        memcpy(&n, &buf[pos + 8], 2);
+        pos += 10;
+        if (km >> (2 * b->k)) return berr(b, LMAT_E_IO, name + ": k-mer wider than 2k bits in record " + std::to_string(i));
+        if (i && km <= prev) return berr(b, LMAT_E_IO, name + ": k-mers not strictly ascending at record " + std::to_string(i));
+        prev = km;
+        if (end - pos < (size_t)n * 4) return berr(b, LMAT_E_IO, name + ": truncated taxid list in record " + std::to_string(i));
+        if (n) {
+            const size_t at = in.nodes.size();
+            in.nodes.resize(at + n);
+            for (u32 j = 0; j < n; ++j) {
+                u32 t;
+                memcpy(&t, &buf[pos + 4 * (size_t)j], 4);
+                auto it = b->node_of.find(t);
+                if (it == b->node_of.end()) return berr(b, LMAT_E_TAXONOMY, name + ": taxid " + std::to_string(t) + " of record " + std::to_string(i) + " is not in the taxonomy tree");
+                in.nodes[at + j] = it->second;
+            }
+            if (n > 1) {
+                chk.assign(in.nodes.begin() + at, in.nodes.end());
+                std::sort(chk.begin(), chk.end());
+                auto dup = std::adjacent_find(chk.begin(), chk.end());
+                if (dup != chk.end()) return berr(b, LMAT_E_IO, name + ": taxid " + std::to_string(b->node_tid[*dup]) + " repeated in the list of record " + std::to_string(i));
+            }
+            in.kmers.push_back(km);      // a record without a list carries nothing
+            in.off.push_back(in.nodes.size());
+        }
+        pos += (size_t)n * 4;
+        if ((i + 1) % 1500 == 0) {
+            if (end - pos < 8 || memcmp(&buf[pos], &test, 8) != 0) return berr(b, LMAT_E_IO, name + ": tax_histo sanity word missing after record " + std::to_string(i));
+            pos += 8;
+        }
+    }
+    if (pos != end) return berr(b, LMAT_E_IO, name + ": " + std::to_string(end - pos) + " bytes behind the last record");
+    return LMAT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -500,6 +868,7 @@ int lmat_build_create(lmat_ctx* ctx, int k, const char* tree_fn, lmat_build** ou
     b->ctx = ctx;
     b->k = k;
     memset(&b->stats, 0, sizeof(b->stats));
+    memset(&b->mstats, 0, sizeof(b->mstats));
     const int rc = load_tree(b, tree_fn);
     if (rc) { lmat::set_err(ctx, rc, b->err); delete b; return rc; }
     *out = b;
@@ -564,6 +933,38 @@ int lmat_build_add_fasta(lmat_build* b, const char* fn) {
     return rc;
 }
 
+int lmat_build_add_taxhisto(lmat_build* b, const char* fn) {
+    if (!b || !fn) return LMAT_E_ARG;
+    if (b->inputs.size() >= 0xFFFFu) return berr(b, LMAT_E_CAPACITY, "at most 65535 tax_histo inputs");
+    lmat_build::Input in;
+    const int rc = parse_taxhisto(b, fn, in);
+    if (rc) return rc;
+    b->inputs.push_back(std::move(in));
+    b->done = false;
+    return LMAT_OK;
+}
+
+int lmat_build_merge_stats(const lmat_build* b, lmat_merge_stats* out) {
+    if (!b || !out) return LMAT_E_ARG;
+    if (!b->done) return LMAT_E_ARG;
+    *out = b->mstats;
+    return LMAT_OK;
+}
+
+int lmat_build_taxid_counts(lmat_build* b, uint32_t* tids, uint64_t* counts, uint64_t cap, uint64_t* n) {
+    if (!b || !n) return LMAT_E_ARG;
+    if (!b->done) return berr(b, LMAT_E_ARG, "lmat_build_run first");
+    u64 m = 0;
+    for (u64 c : b->node_counts) m += c ? 1 : 0;
+    *n = m;
+    if (m > cap) return berr(b, LMAT_E_CAPACITY, "cap below the " + std::to_string(m) + " taxids with a count");
+    if (m && (!tids || !counts)) return LMAT_E_ARG;
+    u64 j = 0;
+    for (size_t i = 0; i < b->node_counts.size(); ++i)
+        if (b->node_counts[i]) { tids[j] = b->node_tid[i]; counts[j++] = b->node_counts[i]; }
+    return LMAT_OK;
+}
+
 int lmat_build_run(lmat_build* b, lmat_build_stats* out) {
     if (!b) return LMAT_E_ARG;
     if (hipSetDevice(b->ctx->device) != hipSuccess) return berr(b, LMAT_E_DEVICE, "hipSetDevice failed");
@@ -622,6 +1023,310 @@ int lmat_build_fetch(lmat_build* b, uint64_t first, uint64_t count, uint64_t* km
 
 namespace {
 
+// bytes of device memory the merge holds per input record and per stored entry of one pass (keys and record numbers twice for the sort, list bounds,
+// flag, position, run start, count, offset, slot, the run's k-mer; the entry as a node and its place in the result)
+constexpr u64 kMergeRecBytes = 72, kMergeEntBytes = 12;
+
+// the most one prefix pass takes of the tax_histo inputs, in bytes of the model above; also checks the 32-bit indices of one pass
+u64 merge_need(const lmat_build* b, int pb, bool& too_many) {
+    too_many = false;
+    if (b->inputs.empty()) return 0;
+    std::vector<u64> rec((size_t)1 << pb, 0), ent((size_t)1 << pb, 0);
+    const int shift = 2 * b->k - pb;
+    for (const auto& in : b->inputs)
+        for (size_t i = 0; i < in.kmers.size(); ++i) {
+            const size_t p = pb ? (size_t)(in.kmers[i] >> shift) : 0;
+            rec[p] += 1;
+            ent[p] += in.off[i + 1] - in.off[i];
+        }
+    u64 need = 0;
+    for (size_t p = 0; p < rec.size(); ++p) {
+        need = std::max(need, rec[p] * kMergeRecBytes + ent[p] * kMergeEntBytes);
+        if (rec[p] > 0x3FFFFFFFull || ent[p] > 0x7FFFFFFFull) too_many = true;
+    }
+    return need;
+}
+
+// The tail of every pass: the merge with the tax_histo inputs (when there are any) and the per-taxid histogram of the final lists.
+struct MergeState {
+    lmat_build* b = nullptr;
+    hipStream_t st = nullptr;
+    bool merging = false;
+    int pb = 0, sb = 1;
+    std::vector<size_t> cursor;           // next record of every input: the passes ascend, an input's slices follow each other
+    std::vector<u32> node_at;
+    DevBuf tin, d_node_at, hist, counters, totals, keysA, keysB, valsA, valsB, rec_off, ent, flag, pos, run, cnt, off, aux, big_run, big_begin, big_end,
+        big_tmp, big_sorted, out, out_km, long_tmp, long_sorted, long_begin, long_end, long_run, temp;
+    const u32 *parent = nullptr, *depth = nullptr, *node_tid = nullptr;
+    u32 n_nodes = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    u64 singletons = 0, entries = 0, longest = 0;
+    ~MergeState() { if (ev[0]) hipEventDestroy(ev[0]); if (ev[1]) hipEventDestroy(ev[1]); }
+
+    hipError_t lap(float& acc) {
+        hipError_t e = hipEventRecord(ev[1], st);
+        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        acc += ms;
+        if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+        return e;
+    }
+
+    int begin(lmat_build* b_, int pb_, const u32* d_parent, const u32* d_depth, const u32* d_node_tid) {
+        b = b_;
+        st = b->ctx->stream;
+        pb = pb_;
+        parent = d_parent;
+        depth = d_depth;
+        node_tid = d_node_tid;
+        n_nodes = (u32)b->node_tid.size();
+        merging = !b->inputs.empty();
+        memset(&b->mstats, 0, sizeof(b->mstats));
+        b->node_counts.assign(n_nodes, 0);
+        BHIP(b, hist.ensure((size_t)n_nodes * 8));
+        BHIP(b, hipMemsetAsync(hist.p, 0, (size_t)n_nodes * 8, st));
+        if (!merging) return LMAT_OK;
+        BHIP(b, hipEventCreate(&ev[0]));
+        BHIP(b, hipEventCreate(&ev[1]));
+        sb = 1;
+        while ((1ull << sb) < b->inputs.size() + 1) ++sb;   // the genomes' own result is the source behind the inputs
+        cursor.assign(b->inputs.size(), 0);
+        node_at.assign(n_nodes, 0);
+        for (u32 i = 0; i < n_nodes; ++i) node_at[b->tin[i]] = i;
+        BHIP(b, tin.ensure((size_t)n_nodes * 4));
+        BHIP(b, d_node_at.ensure((size_t)n_nodes * 4));
+        BHIP(b, counters.ensure(M_TOTAL * 8));
+        BHIP(b, totals.ensure(16));
+        BHIP(b, hipMemcpyAsync(tin.p, b->tin.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, st));
+        BHIP(b, hipMemcpyAsync(d_node_at.p, node_at.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, st));
+        BHIP(b, hipStreamSynchronize(st));
+        b->mstats.inputs = (uint32_t)b->inputs.size();
+        b->mstats.passes = 1u << pb;
+        for (const auto& in : b->inputs) { b->mstats.records_in += in.kmers.size(); b->mstats.entries_in += in.nodes.size(); }
+        return LMAT_OK;
+    }
+
+    // the histogram of a finished CSR on the device
+    int count_lists(const u32* d_tids, u64 n) {
+        if (!n) return LMAT_OK;
+        hipLaunchKernelGGL(hist_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_tids, n, node_tid, n_nodes, hist.as<u64>());
+        BHIP(b, hipGetLastError());
+        return LMAT_OK;
+    }
+
+    // One prefix pass: the inputs' slices and the genomes' result of the pass (gR runs: k-mer, CSR of ascending taxids, runs without a list
+    // included) -> records appended to the builder's result.
+    int pass(u32 pass_no, u32 gR, const u64* g_kmer, const u64* g_off, const u32* g_tids, u64 g_entries) {
+        const int k = b->k;
+        const size_t n_in = b->inputs.size();
+        std::vector<u64> h_keys;
+        std::vector<u32> h_off(1, 0), h_ent;
+        for (size_t s = 0; s < n_in; ++s) {
+            const auto& in = b->inputs[s];
+            const size_t lo = cursor[s];
+            size_t hi = in.kmers.size();
+            if (pb) {
+                const u64 lim = ((u64)pass_no + 1) << (2 * k - pb);   // first k-mer of the next prefix
+                hi = (size_t)(std::lower_bound(in.kmers.begin() + lo, in.kmers.end(), lim) - in.kmers.begin());
+            }
+            cursor[s] = hi;
+            if (hi == lo) continue;
+            const u64 e0 = in.off[lo], e1 = in.off[hi];
+            if (h_ent.size() + (e1 - e0) > 0x7FFFFFFFull || h_keys.size() + (hi - lo) > 0x3FFFFFFFull)
+                return berr(b, LMAT_E_CAPACITY, "more than 2^31 list entries or 2^30 records of the tax_histo inputs in one prefix pass: raise prefix_bits");
+            for (size_t i = lo; i < hi; ++i) {
+                h_keys.push_back((in.kmers[i] << sb) | (u64)s);
+                h_off.push_back((u32)(h_ent.size() + (in.off[i + 1] - e0)));
+            }
+            h_ent.insert(h_ent.end(), in.nodes.begin() + e0, in.nodes.begin() + e1);
+        }
+        const u64 Nin = h_keys.size(), Ein = h_ent.size();
+        const u64 Nr64 = Nin + gR, Ne64 = Ein + g_entries;
+        if (Nr64 == 0) return LMAT_OK;
+        if (Nr64 > 0x7FFFFFFFull || Ne64 > 0xFFFFFF00ull) return berr(b, LMAT_E_CAPACITY, "more than 2^31 records or 2^32 list entries to merge in one prefix pass: raise prefix_bits");
+        const u32 Nr = (u32)Nr64;
+        lmat_merge_stats& M = b->mstats;
+        const u32 slots = (u32)(Ne64 / 65 + 1);   // a side-buffer segment holds more than 64 entries
+        BHIP(b, keysA.ensure((size_t)Nr * 8));
+        BHIP(b, keysB.ensure((size_t)Nr * 8));
+        BHIP(b, valsA.ensure((size_t)Nr * 4));
+        BHIP(b, valsB.ensure((size_t)Nr * 4));
+        BHIP(b, rec_off.ensure(((size_t)Nr + 1) * 4));
+        BHIP(b, ent.ensure((size_t)Ne64 * 4));
+        BHIP(b, flag.ensure((size_t)Nr * 4));
+        BHIP(b, pos.ensure((size_t)Nr * 4));
+        BHIP(b, run.ensure(((size_t)Nr + 1) * 4));
+        BHIP(b, cnt.ensure((size_t)Nr * 8));
+        BHIP(b, off.ensure(((size_t)Nr + 1) * 8));
+        BHIP(b, aux.ensure((size_t)Nr * 4));
+        BHIP(b, out_km.ensure((size_t)Nr * 8));
+        BHIP(b, big_run.ensure((size_t)slots * 4));
+        BHIP(b, big_begin.ensure((size_t)slots * 4));
+        BHIP(b, big_end.ensure((size_t)slots * 4));
+        BHIP(b, hipMemsetAsync(counters.p, 0, M_TOTAL * 8, st));
+        BHIP(b, hipEventRecord(ev[0], st));
+        if (Nin) BHIP(b, hipMemcpyAsync(keysA.p, h_keys.data(), (size_t)Nin * 8, hipMemcpyHostToDevice, st));
+        BHIP(b, hipMemcpyAsync(rec_off.p, h_off.data(), ((size_t)Nin + 1) * 4, hipMemcpyHostToDevice, st));
+        if (Ein) BHIP(b, hipMemcpyAsync(ent.p, h_ent.data(), (size_t)Ein * 4, hipMemcpyHostToDevice, st));
+        const int key_bits = 2 * k + sb;
+        if (gR) {
+            hipLaunchKernelGGL(genome_source_kernel, dim3((gR + 255) / 256), dim3(256), 0, st, gR, g_kmer, g_off, (u32)Nin, (u32)Ein, (u32)n_in, sb, key_bits,
+                               keysA.as<u64>(), rec_off.as<u32>(), counters.as<u64>());
+            BHIP(b, hipGetLastError());
+            if (g_entries) {
+                hipLaunchKernelGGL(tid_to_node_kernel, dim3((u32)((g_entries + 255) / 256)), dim3(256), 0, st, g_tids, g_entries, node_tid, n_nodes, ent.as<u32>() + Ein);
+                BHIP(b, hipGetLastError());
+            }
+        }
+        hipLaunchKernelGGL(iota_kernel, dim3((Nr + 255) / 256), dim3(256), 0, st, valsA.as<u32>(), Nr);
+        BHIP(b, hipGetLastError());
+        BHIP(b, hipStreamSynchronize(st));   // the host vectors go out of use here
+        BHIP(b, lap(M.upload_ms));
+
+        // ---- one key per record, sorted by (k-mer, source); records without a list behind all others
+        {
+            size_t tb = 0;
+            BHIP(b, rocprim::radix_sort_pairs(nullptr, tb, keysA.as<u64>(), keysB.as<u64>(), valsA.as<u32>(), valsB.as<u32>(), Nr, 0, key_bits + 1, st));
+            BHIP(b, temp.ensure(tb));
+            BHIP(b, rocprim::radix_sort_pairs(temp.p, tb, keysA.as<u64>(), keysB.as<u64>(), valsA.as<u32>(), valsB.as<u32>(), Nr, 0, key_bits + 1, st));
+        }
+        u64 hc[M_TOTAL];
+        BHIP(b, hipMemcpyAsync(hc, counters.p, M_TOTAL * 8, hipMemcpyDeviceToHost, st));
+        BHIP(b, lap(M.sort_ms));
+        const u32 Nv = Nr - (u32)hc[M_EMPTY];
+        if (Nv == 0) return LMAT_OK;
+
+        // ---- runs of one k-mer
+        const u32 gridN = (Nv + 255) / 256;
+        hipLaunchKernelGGL(mseg_flag_kernel, dim3(gridN), dim3(256), 0, st, keysB.as<u64>(), Nv, sb, flag.as<u32>());
+        BHIP(b, hipGetLastError());
+        {
+            size_t tb = 0;
+            BHIP(b, rocprim::exclusive_scan(nullptr, tb, flag.as<u32>(), pos.as<u32>(), 0u, (size_t)Nv, rocprim::plus<u32>(), st));
+            BHIP(b, temp.ensure(tb));
+            BHIP(b, rocprim::exclusive_scan(temp.p, tb, flag.as<u32>(), pos.as<u32>(), 0u, (size_t)Nv, rocprim::plus<u32>(), st));
+        }
+        hipLaunchKernelGGL(mseg_scatter_kernel, dim3(gridN), dim3(256), 0, st, flag.as<u32>(), pos.as<u32>(), Nv, run.as<u32>(), totals.as<u64>());
+        BHIP(b, hipGetLastError());
+        u64 tot[2];
+        BHIP(b, hipMemcpyAsync(tot, totals.p, 16, hipMemcpyDeviceToHost, st));
+        BHIP(b, lap(M.segment_ms));
+        const u32 R = (u32)tot[0];
+
+        // ---- union: classify, side-buffer segments in tour order, count, scan, write
+        UnionArgs ua;
+        memset(&ua, 0, sizeof(ua));
+        ua.R = R;
+        ua.run_start = run.as<u32>();
+        ua.rec = valsB.as<u32>();
+        ua.rec_off = rec_off.as<u32>();
+        ua.ent = ent.as<u32>();
+        ua.tin = tin.as<u32>();
+        ua.node_at = d_node_at.as<u32>();
+        ua.parent = parent;
+        ua.depth = depth;
+        ua.node_tid = node_tid;
+        ua.aux = aux.as<u32>();
+        ua.big_run = big_run.as<u32>();
+        ua.big_begin = big_begin.as<u32>();
+        ua.big_end = big_end.as<u32>();
+        ua.cnt = cnt.as<u64>();
+        ua.counters = counters.as<u64>();
+        hipLaunchKernelGGL(union_classify_kernel, dim3((R + 255) / 256), dim3(256), 0, st, ua);
+        BHIP(b, hipGetLastError());
+        BHIP(b, hipMemcpyAsync(hc, counters.p, M_TOTAL * 8, hipMemcpyDeviceToHost, st));
+        BHIP(b, hipStreamSynchronize(st));
+        const u64 n_big = hc[M_BIG_RUNS], big_entries = hc[M_BIG_ENTRIES];
+        if (n_big) {
+            BHIP(b, big_tmp.ensure(big_entries * 4));
+            BHIP(b, big_sorted.ensure(big_entries * 4));
+            hipLaunchKernelGGL(big_gather_kernel, dim3((u32)n_big), dim3(256), 0, st, ua, big_tmp.as<u32>());
+            BHIP(b, hipGetLastError());
+            size_t tb = 0;
+            BHIP(b, rocprim::segmented_radix_sort_keys(nullptr, tb, big_tmp.as<u32>(), big_sorted.as<u32>(), (unsigned)big_entries, (unsigned)n_big,
+                                                       big_begin.as<u32>(), big_end.as<u32>(), 0, 32, st));
+            BHIP(b, temp.ensure(tb));
+            BHIP(b, rocprim::segmented_radix_sort_keys(temp.p, tb, big_tmp.as<u32>(), big_sorted.as<u32>(), (unsigned)big_entries, (unsigned)n_big,
+                                                       big_begin.as<u32>(), big_end.as<u32>(), 0, 32, st));
+            ua.big_sorted = big_sorted.as<u32>();
+        }
+        const u32 gridR = (u32)(((u64)R + 64 * kWavesPerBlock - 1) / (64 * kWavesPerBlock));
+        hipLaunchKernelGGL(union_kernel<false>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ua);
+        BHIP(b, hipGetLastError());
+        {
+            size_t tb = 0;
+            BHIP(b, rocprim::exclusive_scan(nullptr, tb, cnt.as<u64>(), off.as<u64>(), 0ull, (size_t)R, rocprim::plus<u64>(), st));
+            BHIP(b, temp.ensure(tb));
+            BHIP(b, rocprim::exclusive_scan(temp.p, tb, cnt.as<u64>(), off.as<u64>(), 0ull, (size_t)R, rocprim::plus<u64>(), st));
+        }
+        BHIP(b, hipMemcpyAsync(hc, counters.p, M_TOTAL * 8, hipMemcpyDeviceToHost, st));
+        BHIP(b, hipStreamSynchronize(st));
+        if (hc[C_TOOLONG])
+            return berr(b, LMAT_E_CAPACITY, "a merged taxid list of " + std::to_string(hc[C_TOOLONG]) + " entries: the tax_histo record holds at most 65535");
+        const u64 n_entries = hc[C_ENTRIES], n_long = hc[C_LONG_RUNS], long_entries = hc[C_LONG_ENTRIES];
+        if (long_entries > 0xFFFFFFF0ull) return berr(b, LMAT_E_CAPACITY, "more than 2^32 entries in lists beyond 64 taxids in one pass: raise prefix_bits");
+        BHIP(b, hipMemcpyAsync(off.as<u64>() + R, &n_entries, 8, hipMemcpyHostToDevice, st));
+        BHIP(b, out.ensure(n_entries * 4));
+        if (n_long) {
+            BHIP(b, long_tmp.ensure(long_entries * 4));
+            BHIP(b, long_sorted.ensure(long_entries * 4));
+            BHIP(b, long_begin.ensure(n_long * 4));
+            BHIP(b, long_end.ensure(n_long * 4));
+            BHIP(b, long_run.ensure(n_long * 4));
+        }
+        BHIP(b, hipMemsetAsync(counters.as<u64>() + C_LONG_RUNS, 0, 16, st));   // the write pass hands out the long lists' places with them
+        ua.off = off.as<u64>();
+        ua.tids = out.as<u32>();
+        ua.long_tmp = long_tmp.as<u32>();
+        ua.long_begin = long_begin.as<u32>();
+        ua.long_end = long_end.as<u32>();
+        ua.long_run = long_run.as<u32>();
+        hipLaunchKernelGGL(union_kernel<true>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ua);
+        BHIP(b, hipGetLastError());
+        if (n_long) {
+            size_t tb = 0;
+            BHIP(b, rocprim::segmented_radix_sort_keys(nullptr, tb, long_tmp.as<u32>(), long_sorted.as<u32>(), (unsigned)long_entries, (unsigned)n_long,
+                                                       long_begin.as<u32>(), long_end.as<u32>(), 0, 32, st));
+            BHIP(b, temp.ensure(tb));
+            BHIP(b, rocprim::segmented_radix_sort_keys(temp.p, tb, long_tmp.as<u32>(), long_sorted.as<u32>(), (unsigned)long_entries, (unsigned)n_long,
+                                                       long_begin.as<u32>(), long_end.as<u32>(), 0, 32, st));
+            hipLaunchKernelGGL(long_copy_kernel, dim3((u32)n_long), dim3(256), 0, st, long_sorted.as<u32>(), long_begin.as<u32>(), long_end.as<u32>(),
+                               long_run.as<u32>(), off.as<u64>(), out.as<u32>());
+            BHIP(b, hipGetLastError());
+        }
+        const u64 kmask = (1ull << (2 * k)) - 1;
+        hipLaunchKernelGGL(mrun_kmer_kernel, dim3((R + 255) / 256), dim3(256), 0, st, keysB.as<u64>(), run.as<u32>(), R, sb, kmask, out_km.as<u64>());
+        BHIP(b, hipGetLastError());
+        BHIP(b, lap(M.union_ms));
+        const int rc = count_lists(out.as<u32>(), n_entries);
+        if (rc) return rc;
+        BHIP(b, lap(M.histogram_ms));
+
+        // ---- to the host: every run has a list
+        std::vector<u64> h_o((size_t)R + 1);
+        const size_t k0 = b->kmers.size(), t0 = b->tids.size();
+        b->kmers.resize(k0 + R);
+        b->tids.resize(t0 + n_entries);
+        BHIP(b, hipMemcpy(b->kmers.data() + k0, out_km.p, (size_t)R * 8, hipMemcpyDeviceToHost));
+        BHIP(b, hipMemcpy(h_o.data(), off.p, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost));
+        if (n_entries) BHIP(b, hipMemcpy(b->tids.data() + t0, out.p, n_entries * 4, hipMemcpyDeviceToHost));
+        for (u32 r = 0; r < R; ++r) b->list_off.push_back(t0 + h_o[r + 1]);
+        M.records_one_source += hc[M_ONE];
+        M.records_merged += hc[M_MERGED];
+        M.records_grown += hc[M_GROWN];
+        singletons += hc[C_SINGLETONS];
+        entries += n_entries;
+        longest = std::max<u64>(longest, hc[C_LONGEST]);
+        return LMAT_OK;
+    }
+
+    int finish() {
+        if (n_nodes) BHIP(b, hipMemcpy(b->node_counts.data(), hist.p, (size_t)n_nodes * 8, hipMemcpyDeviceToHost));
+        return LMAT_OK;
+    }
+};
+
 int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
     lmat_ctx* c = b->ctx;
     hipStream_t st = c->stream;
@@ -635,7 +1340,10 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
     const u64 T = b->text.size();
     const u32 n_rec = (u32)b->rec_start.size();
     if (b->rec_start.size() > 0x7FFFFFFFull) return berr(b, LMAT_E_CAPACITY, "more than 2^31 FASTA records");
-    if (T == 0 || n_rec == 0) return LMAT_OK;
+    const bool merging = !b->inputs.empty();
+    b->node_counts.assign(b->node_tid.size(), 0);
+    memset(&b->mstats, 0, sizeof(b->mstats));
+    if ((T == 0 || n_rec == 0) && !merging) return LMAT_OK;
 
     // owners: distinct taxids; the tree's own in Euler-tour order, the others behind them
     std::vector<u32> owners(b->rec_taxid);
@@ -671,12 +1379,12 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
         BHIP(b, hipMemGetInfo(&fr, &tot));
         budget = fr / 2;
     }
-    const u32 chunk = b->chunk_bases ? std::max<u32>(b->chunk_bases, 1024) : (1u << 24);
+    const u32 chunk = T == 0 ? 1024u : b->chunk_bases ? std::max<u32>(b->chunk_bases, 1024) : (1u << 24);   // T == 0: a merge of tax_histo inputs alone
     const u64 chunk_waves = ((u64)chunk + kSpan - 1) / kSpan;
     const u64 chunk_alloc = chunk_waves * kSpan + kLead + 64;
     const u64 fixed = chunk_alloc + (u64)n_rec * 12 + (u64)b->node_tid.size() * 12 + (u64)n_owner * 4 + (64u << 20);   // + sort scratch and slack
     const u64 per_pair = 8 + 8 + 8 + 8 + 8 + 4 + 4 + (packed ? 0 : 8) + 16;   // keys x2, flag, pos, distinct pair, run start, (vals x2), list entries (estimate)
-    if (budget <= fixed + per_pair * 1024) return berr(b, LMAT_E_NOMEM, "device budget of " + std::to_string(budget) + " bytes is below the fixed buffers");
+    if (budget <= fixed || (budget <= fixed + per_pair * 1024 && T != 0)) return berr(b, LMAT_E_NOMEM, "device budget of " + std::to_string(budget) + " bytes is below the fixed buffers");
     u64 cap = std::min<u64>((budget - fixed) / per_pair, 0x7FFFFF00ull);
     int pb = pb_forced;
     if (pb < 0) {
@@ -684,6 +1392,24 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
         pb = pb_start;
         while (pb < std::min(2 * k, 24) && (double)T * 2.0 / (double)(1ull << pb) > (double)cap && T > cap) ++pb;
         if (pb == 0 && T > cap) pb = 1;
+    }
+    if (merging) {
+        // The slices of the inputs are known exactly; what they take of a pass comes off the budget first, the pairs of the genomes share the rest
+        // with the records and entries their own result adds to the merge (at most one record per pair, lists as the estimate above has them).
+        const u64 avail = budget - fixed;
+        const u64 per_pair_m = per_pair + kMergeRecBytes + 2 * kMergeEntBytes;
+        const int pb_max = std::min(2 * k, 24);
+        for (pb = pb_forced < 0 ? pb_start : pb_forced;; ++pb) {
+            bool too_many = false;
+            const u64 need = merge_need(b, pb, too_many);
+            const bool in_fit = !too_many && need + (T ? per_pair_m * 1024 : 0) < avail;
+            if (in_fit) cap = std::min<u64>((avail - need) / per_pair_m, 0x7FFFFF00ull);
+            const bool seq_fit = in_fit && (T <= cap || (double)T * 2.0 / (double)(1ull << pb) <= (double)cap);
+            if (in_fit && (seq_fit || pb_forced >= 0)) break;   // a forced split that the genomes overflow is found by the extraction, as without inputs
+            if (pb_forced >= 0 || pb >= pb_max)
+                return berr(b, LMAT_E_CAPACITY, "the tax_histo inputs take " + std::to_string(need) + " bytes in one of the " + std::to_string(1ull << pb) +
+                                                   " prefix passes, the device budget leaves " + std::to_string(avail) + ": raise the budget or prefix_bits");
+        }
     }
     cap = std::min<u64>(cap, T);   // no pass emits more pairs than there are bases
     S.prefix_bits = (uint32_t)pb;
@@ -708,9 +1434,11 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
     BHIP(b, d_dk.ensure(cap * 8));
     BHIP(b, d_do.ensure(cap * 4));
     BHIP(b, d_run.ensure((cap + 1) * 4));
-    BHIP(b, hipMemcpyAsync(d_rec_start.p, b->rec_start.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
-    BHIP(b, hipMemcpyAsync(d_rec_owner.p, rec_owner.data(), (size_t)n_rec * 4, hipMemcpyHostToDevice, st));
-    BHIP(b, hipMemcpyAsync(d_owner_node.p, owner_node.data(), (size_t)n_owner * 4, hipMemcpyHostToDevice, st));
+    if (n_rec) {
+        BHIP(b, hipMemcpyAsync(d_rec_start.p, b->rec_start.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
+        BHIP(b, hipMemcpyAsync(d_rec_owner.p, rec_owner.data(), (size_t)n_rec * 4, hipMemcpyHostToDevice, st));
+        BHIP(b, hipMemcpyAsync(d_owner_node.p, owner_node.data(), (size_t)n_owner * 4, hipMemcpyHostToDevice, st));
+    }
     BHIP(b, hipMemcpyAsync(d_parent.p, b->parent.data(), b->parent.size() * 4, hipMemcpyHostToDevice, st));
     BHIP(b, hipMemcpyAsync(d_depth.p, b->depth.data(), b->depth.size() * 4, hipMemcpyHostToDevice, st));
     BHIP(b, hipMemcpyAsync(d_node_tid.p, b->node_tid.data(), b->node_tid.size() * 4, hipMemcpyHostToDevice, st));
@@ -731,6 +1459,10 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
         if (e == hipSuccess) e = hipEventRecord(ev[0], st);
         return e;
     };
+
+    // the per-taxid histogram of the final lists, and the merge with the tax_histo inputs when there are any
+    MergeState tail;
+    if (const int rc = tail.begin(b, pb, d_parent.as<u32>(), d_depth.as<u32>(), d_node_tid.as<u32>())) return rc;
 
     u64 host_c[C_N];
     for (u32 pass = 0; pass < (1u << pb); ++pass) {
@@ -777,7 +1509,10 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
         const u64 N = host_c[C_CURSOR];
         if (pass == 0) S.windows = host_c[C_WINDOWS];   // every pass sees every window; only the emitted pairs differ
         S.emitted_pairs += N;
-        if (N == 0) continue;
+        if (N == 0) {
+            if (merging) if (const int rc = tail.pass(pass, 0, nullptr, nullptr, nullptr, 0)) return rc;
+            continue;
+        }
 
         // ---- sort by (k-mer, owner)
         Sorted sorted;
@@ -887,6 +1622,12 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
         hipLaunchKernelGGL(run_kmer_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d_dk.as<u64>(), d_run.as<u32>(), R, d_pos.as<u64>());
         BHIP(b, hipGetLastError());
         BHIP(b, lap(S.closure_ms));
+        if (merging) {   // the pass's result stays on the device and is one more source of the merge
+            if (const int rc = tail.pass(pass, R, d_pos.as<u64>(), d_off.as<u64>(), d_tids.as<u32>(), entries)) return rc;
+            S.dropped_unknown += host_c[C_DROPPED];
+            continue;
+        }
+        if (const int rc = tail.count_lists(d_tids.as<u32>(), entries)) return rc;
 
         // ---- to the host: records without a known owner are left out (tax_histo.cpp:239-248)
         std::vector<u64> h_km(R), h_off((size_t)R + 1);
@@ -906,7 +1647,12 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
         S.longest_list = std::max<u64>(S.longest_list, host_c[C_LONGEST]);
     }
     S.records_written = b->kmers.size();
-    return LMAT_OK;
+    if (merging) {   // these four describe the merged result
+        S.singletons = tail.singletons;
+        S.total_list_entries = tail.entries;
+        S.longest_list = tail.longest;
+    }
+    return tail.finish();
 }
 
 }  // namespace
