@@ -22,6 +22,9 @@
 //   union_kernel<count>, exclusive scan, union_kernel<write>: a one-source list is copied, the others are the closure of the union
 //   of the stored entries taken as owners -- the same virtual-tree walk over the entries in Euler-tour order, equal neighbours dropped.
 // hist_kernel counts, for either kind of run, the result records whose list holds each taxid (countTaxidFrequency's map).
+//
+// Written once for both: the walk (closure_walk, over a sequence accessor: OwnerSeq for the build, TourSeq for the merge) with claim_long,
+// count_list and rank_store around it on the device; on the host the count -> CSR tail (write_lists), with_temp, LapTimer and write_records.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -56,6 +59,14 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
+
+template <class T, class Op> __device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = op(v, (T)__shfl_xor(v, d));
+    return v;
+}
+template <class T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T x, T y) { return x + y; }); }
+template <class T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, [](T x, T y) { return x > y ? x : y; }); }
 
 // reverse complement of a k-mer held in the low 2k bits (Encoder::rc): 2-bit groups reversed, complemented
 __device__ __forceinline__ u64 revcomp(u64 x, int k) {
@@ -169,8 +180,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void extract_kernel(ExtractArg
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) n_windows += __shfl_xor(n_windows, d);
+    n_windows = wave_sum(n_windows);
     if (lane == 0 && n_windows) atomicAdd(&a.counters[C_WINDOWS], n_windows);
 }
 
@@ -225,33 +235,118 @@ __global__ __launch_bounds__(256) void run_kmer_kernel(const u64* d_kmer, const 
     if (r < R) out[r] = d_kmer[run_start[r]];
 }
 
+// ------------------------------------------------------------------------- what the closure and the union kernel share
+struct TreeArgs {
+    const u32* parent;       // [n_nodes] dense; the root is its own parent
+    const u32* depth;        // [n_nodes]
+    const u32* node_tid;     // [n_nodes] ascending with the dense index
+};
+
+struct LongArgs {            // write pass: lists of more than 64 entries, unsorted, to be sorted by segment
+    u32* tmp;
+    u32* begin;              // [n_long] segment bounds in tmp
+    u32* end;
+    u32* run;                // [n_long] the run of the segment
+};
+
+// depth-levelled parent walk
+__device__ __forceinline__ u32 lca2(const TreeArgs& t, u32 a, u32 b) {
+    u32 da = t.depth[a], db = t.depth[b];
+    while (da > db) { a = t.parent[a]; --da; }
+    while (db > da) { b = t.parent[b]; --db; }
+    while (a != b) { a = t.parent[a]; b = t.parent[b]; }
+    return a;
+}
+
+// The closure of a sequence of n nodes in Euler-tour order, by the whole wave, 64 elements a step: the first element walks up to and including
+// the LCA of the first and the last, every later one up to -- not including -- its LCA with the element before it; an element the sequence
+// reports as a repeat of the one before it adds nothing.  Returns the length of the closure; the write pass stores its taxids, unordered,
+// from dst on.  distinct = the elements that are no repeats.
+template <bool WRITE, class Seq>
+__device__ __forceinline__ u32 closure_walk(const TreeArgs& t, const Seq& seq, u32 n, u32 lane, u32* dst, u32& distinct) {
+    const u32 top = lca2(t, seq.node(0), seq.node(n - 1));
+    u32 total = 0;
+    distinct = 0;
+    for (u32 base = 0; base < n; base += 64) {
+        const u32 j = base + lane;
+        u32 node = 0, len = 0;
+        bool fresh = false;
+        if (j < n) {
+            node = seq.node(j);
+            fresh = j == 0 || !seq.repeat(j);
+            if (j == 0) len = t.depth[node] - t.depth[top] + 1;
+            else if (fresh) len = t.depth[node] - t.depth[lca2(t, seq.node(j - 1), node)];
+        }
+        u32 incl = len;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 o = __shfl_up(incl, d);
+            if ((int)lane >= d) incl += o;
+        }
+        if (WRITE) {
+            u32 at = total + incl - len;
+            for (u32 x = node, i = 0; i < len; ++i, x = t.parent[x]) dst[at++] = t.node_tid[x];
+        }
+        total += __shfl(incl, 63);
+        distinct += __popcll(__ballot(fresh));
+    }
+    return total;
+}
+
+// write pass: the segment of the side buffer for run rr's list of n > 64 entries, claimed by lane 0 with the two long-list counters
+__device__ __forceinline__ u32* claim_long(const LongArgs& lg, u64* counters, u32 rr, u32 n, u32 lane) {
+    u32 at = 0;
+    if (lane == 0) {
+        const u32 slot = (u32)atomicAdd(&counters[C_LONG_RUNS], 1ull);
+        at = (u32)atomicAdd(&counters[C_LONG_ENTRIES], (u64)n);
+        lg.begin[slot] = at;
+        lg.end[slot] = at + n;
+        lg.run[slot] = rr;
+    }
+    return lg.tmp + __shfl(at, 0);
+}
+
+// count pass, one lane: the length of a list the wave made, and what the pass's counters say about it
+__device__ __forceinline__ void count_list(u64* cnt, u64* counters, u32 rr, u32 total) {
+    cnt[rr] = total;
+    atomicAdd(&counters[C_ENTRIES], (u64)total);
+    atomicMax(&counters[C_LONGEST], (u64)total);
+    if (total == 1) atomicAdd(&counters[C_SINGLETONS], 1ull);
+    if (total > kMaxList) atomicMax(&counters[C_TOOLONG], (u64)total);
+    if (total > 64) { atomicAdd(&counters[C_LONG_RUNS], 1ull); atomicAdd(&counters[C_LONG_ENTRIES], (u64)total); }
+}
+
+// write pass: the n <= 64 distinct entries of the wave's stage in ascending order to out; the rank of one is the number of smaller ones
+__device__ __forceinline__ void rank_store(const u32* stage, u32 n, u32 lane, u32* out) {
+    wave_sync();
+    const u32 v = lane < n ? stage[lane] : 0xFFFFFFFFu;
+    u32 rank = 0;
+    for (u32 t = 0; t < n; ++t) rank += stage[t] < v ? 1u : 0u;
+    if (lane < n) out[rank] = v;
+    wave_sync();
+}
+
+// ------------------------------------------------------------------------------------------------------------- the build
 struct ClosureArgs {
     u32 R;
     const u32* run_start;    // [R + 1]
     const u32* d_owner;      // distinct owners of every run, in Euler-tour order, unknown owners last
     u32 n_known;             // owner indices below this are tree nodes
     const u32* owner_node;   // [n_owner] dense node index
-    const u32* parent;       // [n_nodes] dense; the root is its own parent
-    const u32* depth;        // [n_nodes]
-    const u32* node_tid;     // [n_nodes] ascending with the dense index
+    TreeArgs tree;
     u64* cnt;                // count pass: [R] list length
     const u64* off;          // write pass: [R + 1]
     u32* tids;               // write pass: the CSR
-    u32* long_tmp;           // write pass: lists of more than 64 entries, unsorted, to be sorted by segment
-    u32* long_begin;         // [n_long] segment bounds in long_tmp
-    u32* long_end;
-    u32* long_run;           // [n_long] the run of the segment
+    LongArgs lng;
     u64* counters;
 };
 
-// depth-levelled parent walk
-__device__ __forceinline__ u32 lca2(const u32* parent, const u32* depth, u32 a, u32 b) {
-    u32 da = depth[a], db = depth[b];
-    while (da > db) { a = parent[a]; --da; }
-    while (db > da) { b = parent[b]; --db; }
-    while (a != b) { a = parent[a]; b = parent[b]; }
-    return a;
-}
+struct OwnerSeq {            // the owners of one run the tree knows: distinct, in tour order
+    const u32* owner_node;
+    const u32* owner;
+    __device__ __forceinline__ u32 node(u32 j) const { return owner_node[owner[j]]; }
+    __device__ __forceinline__ bool repeat(u32) const { return false; }
+};
 
 // One run per lane.  Runs whose list is one taxid (a single owner, or a single owner the tree knows) and runs without a known
 // owner are settled by their lane; the others are taken one after the other by the whole wave, owners on the lanes (several
@@ -273,7 +368,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void closure_kernel(ClosureArg
         if (first >= a.n_known) kind = 0;
         else if (e - s == 1 || a.d_owner[s + 1] >= a.n_known) kind = 1;
         else kind = 2;
-        if (kind == 1 && WRITE) a.tids[a.off[r]] = a.node_tid[a.owner_node[first]];
+        if (kind == 1 && WRITE) a.tids[a.off[r]] = a.tree.node_tid[a.owner_node[first]];
         if (kind < 2 && !WRITE) a.cnt[r] = (u64)kind;
     }
     if (!WRITE) {
@@ -296,65 +391,17 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void closure_kernel(ClosureArg
             g += __popcll(ok);
             if (ok != ~0ull) break;
         }
-        const u32 top = lca2(a.parent, a.depth, a.owner_node[a.d_owner[rs]], a.owner_node[a.d_owner[rs + g - 1]]);
         u32 n = 0;
-        bool is_long = false;
-        u32 long_at = 0, long_slot = 0;
-        u32* dst = nullptr;
+        u32* dst = WRITE ? &s_stage[wv][0] : nullptr;
         if (WRITE) {
             n = (u32)(a.off[rr + 1] - a.off[rr]);
-            is_long = n > 64;
-            if (is_long) {
-                if (lane == 0) {
-                    long_slot = (u32)atomicAdd(&a.counters[C_LONG_RUNS], 1ull);
-                    long_at = (u32)atomicAdd(&a.counters[C_LONG_ENTRIES], (u64)n);
-                    a.long_begin[long_slot] = long_at;
-                    a.long_end[long_slot] = long_at + n;
-                    a.long_run[long_slot] = rr;
-                }
-                long_at = __shfl(long_at, 0);
-                dst = a.long_tmp + long_at;
-            } else dst = &s_stage[wv][0];
+            if (n > 64) dst = claim_long(a.lng, a.counters, rr, n, lane);
         }
-        u32 total = 0;
-        for (u32 base = 0; base < g; base += 64) {
-            const u32 j = base + lane;
-            u32 node = 0, len = 0;
-            if (j < g) {
-                node = a.owner_node[a.d_owner[rs + j]];
-                if (j == 0) len = a.depth[node] - a.depth[top] + 1;
-                else len = a.depth[node] - a.depth[lca2(a.parent, a.depth, a.owner_node[a.d_owner[rs + j - 1]], node)];
-            }
-            u32 incl = len;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const u32 o = __shfl_up(incl, d);
-                if ((int)lane >= d) incl += o;
-            }
-            if (WRITE) {
-                u32 at = total + incl - len;
-                for (u32 x = node, i = 0; i < len; ++i, x = a.parent[x]) dst[at++] = a.node_tid[x];
-            }
-            total += __shfl(incl, 63);
-        }
+        u32 distinct;
+        const u32 total = closure_walk<WRITE>(a.tree, OwnerSeq{a.owner_node, a.d_owner + rs}, g, lane, dst, distinct);
         if (!WRITE) {
-            if (lane == 0) {
-                a.cnt[rr] = total;
-                atomicAdd(&a.counters[C_ENTRIES], (u64)total);
-                atomicMax(&a.counters[C_LONGEST], (u64)total);
-                if (total == 1) atomicAdd(&a.counters[C_SINGLETONS], 1ull);
-                if (total > kMaxList) atomicMax(&a.counters[C_TOOLONG], (u64)total);
-                if (total > 64) { atomicAdd(&a.counters[C_LONG_RUNS], 1ull); atomicAdd(&a.counters[C_LONG_ENTRIES], (u64)total); }
-            }
-        } else if (!is_long) {
-            // ascending order within the wave: the entries are distinct, the rank of one is the number of smaller ones
-            wave_sync();
-            const u32 v = lane < n ? s_stage[wv][lane] : 0xFFFFFFFFu;
-            u32 rank = 0;
-            for (u32 t = 0; t < n; ++t) rank += s_stage[wv][t] < v ? 1u : 0u;
-            if (lane < n) a.tids[a.off[rr] + rank] = v;
-            wave_sync();
-        }
+            if (lane == 0) count_list(a.cnt, a.counters, rr, total);
+        } else if (n <= 64) rank_store(&s_stage[wv][0], n, lane, a.tids + a.off[rr]);
     }
 }
 
@@ -435,10 +482,8 @@ struct UnionArgs {
     const u32* ent;          // dense node index of every stored entry
     const u32* tin;          // [n_nodes] Euler-tour entry time of the node
     const u32* node_at;      // [n_nodes] its inverse
-    const u32* parent;
-    const u32* depth;
-    const u32* node_tid;
-    u32* aux;                // [R] runs with several sources: kSmall, or the slot of the side-buffer segment
+    TreeArgs tree;
+    u32* aux;               // [R] runs with several sources: kSmall, or the slot of the side-buffer segment
     u32* big_run;            // [slots]
     u32* big_begin;          // [slots] segment of the gathered tour indices
     u32* big_end;
@@ -446,18 +491,16 @@ struct UnionArgs {
     u64* cnt;                // [R]
     const u64* off;          // write pass: [R + 1]
     u32* tids;
-    u32* long_tmp;
-    u32* long_begin;
-    u32* long_end;
-    u32* long_run;
+    LongArgs lng;
     u64* counters;
 };
 
-template <class T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
+struct TourSeq {             // tour indices in order; equal neighbours are one entry
+    const u32* node_at;
+    const u32* tour;
+    __device__ __forceinline__ u32 node(u32 j) const { return node_at[tour[j]]; }
+    __device__ __forceinline__ bool repeat(u32 j) const { return tour[j] == tour[j - 1]; }
+};
 
 // One run per lane.  A run with one source has its list's length (a copy follows); a run with several gets kSmall when the entries of all its
 // lists together fit the 64 lanes, else a segment of the side buffer, filled by big_gather_kernel and ordered by rocPRIM's segmented sort.
@@ -486,9 +529,7 @@ __global__ __launch_bounds__(256) void union_classify_kernel(UnionArgs a) {
     const u32 n_one = __popcll(__ballot(one)), n_multi = __popcll(__ballot(active && ns > 1)), n_single = __popcll(__ballot(one && G == 1));
     const u32 n_long = __popcll(__ballot(one && G > 64));
     const u64 entries = wave_sum<u64>(one ? G : 0), long_entries = wave_sum<u64>(one && G > 64 ? G : 0);
-    u32 longest = one ? G : 0;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) longest = max(longest, (u32)__shfl_xor(longest, d));
+    const u32 longest = wave_max<u32>(one ? G : 0);
     if (lane_id() == 0) {
         if (n_one) { atomicAdd(&a.counters[M_ONE], (u64)n_one); atomicAdd(&a.counters[C_ENTRIES], entries); atomicMax(&a.counters[C_LONGEST], (u64)longest); }
         if (n_multi) atomicAdd(&a.counters[M_MERGED], (u64)n_multi);
@@ -510,7 +551,7 @@ __global__ __launch_bounds__(256) void big_gather_kernel(UnionArgs a, u32* big_t
 
 // One run per lane.  One source: the list is copied -- by the lane while it ascends (a list this builder wrote), else by the wave, ranked; beyond
 // 64 entries through the side buffer of the long lists.  Several sources: the wave orders the entries of all lists by tour index (in LDS, or
-// the segment sorted beforehand), equal neighbours are one entry, and the walk of closure_kernel gives the closure in disjoint pieces.
+// the segment sorted beforehand), equal neighbours are one entry, and closure_walk gives the closure in disjoint pieces.
 template <bool WRITE>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void union_kernel(UnionArgs a) {
     __shared__ u32 s_stage[kWavesPerBlock][64];   // gathered tour indices, later the list to be ranked
@@ -535,7 +576,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void union_kernel(UnionArgs a)
                 for (u32 i = 0; i < n; ++i) {
                     const u32 x = a.ent[b0 + i];
                     if (i && x <= prev) { wave_job = true; break; }
-                    dst[i] = a.node_tid[x];
+                    dst[i] = a.tree.node_tid[x];
                     prev = x;
                 }
             }
@@ -547,27 +588,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void union_kernel(UnionArgs a)
         jobs &= jobs - 1;
         const u32 rs = __shfl(s, b), re = __shfl(e, b), rr = __shfl(r, b);
         u32 n = 0;
-        bool is_long = false;
-        u32 long_at = 0;
         u32* dst = &s_stage[wv][0];
         if (WRITE) {
             n = (u32)(a.off[rr + 1] - a.off[rr]);
-            is_long = n > 64;
-            if (is_long) {
-                if (lane == 0) {
-                    const u32 slot = (u32)atomicAdd(&a.counters[C_LONG_RUNS], 1ull);
-                    long_at = (u32)atomicAdd(&a.counters[C_LONG_ENTRIES], (u64)n);
-                    a.long_begin[slot] = long_at;
-                    a.long_end[slot] = long_at + n;
-                    a.long_run[slot] = rr;
-                }
-                long_at = __shfl(long_at, 0);
-                dst = a.long_tmp + long_at;
-            }
+            if (n > 64) dst = claim_long(a.lng, a.counters, rr, n, lane);
         }
         if (re - rs == 1) {   // write pass only: the copy of a list that does not ascend or is long
             const u32 q = a.rec[rs], b0 = a.rec_off[q];
-            for (u32 i = lane; i < n; i += 64) dst[i] = a.node_tid[a.ent[b0 + i]];
+            for (u32 i = lane; i < n; i += 64) dst[i] = a.tree.node_tid[a.ent[b0 + i]];
         } else {
             const u32 slot = a.aux[rr];
             const u32* seq;
@@ -591,54 +619,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void union_kernel(UnionArgs a)
                 seq = a.big_sorted + a.big_begin[slot];
                 G = a.big_end[slot] - a.big_begin[slot];
             }
-            const u32 top = lca2(a.parent, a.depth, a.node_at[seq[0]], a.node_at[seq[G - 1]]);
-            u32 total = 0, distinct = 0;
-            for (u32 base = 0; base < G; base += 64) {
-                const u32 j = base + lane;
-                u32 node = 0, len = 0;
-                bool fresh = false;
-                if (j < G) {
-                    const u32 t = seq[j];
-                    node = a.node_at[t];
-                    if (j == 0) { len = a.depth[node] - a.depth[top] + 1; fresh = true; }
-                    else {
-                        const u32 tp = seq[j - 1];
-                        fresh = tp != t;
-                        if (fresh) len = a.depth[node] - a.depth[lca2(a.parent, a.depth, a.node_at[tp], node)];
-                    }
-                }
-                u32 incl = len;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const u32 o = __shfl_up(incl, d);
-                    if ((int)lane >= d) incl += o;
-                }
-                if (WRITE) {
-                    u32 at = total + incl - len;
-                    for (u32 x = node, i = 0; i < len; ++i, x = a.parent[x]) dst[at++] = a.node_tid[x];
-                }
-                total += __shfl(incl, 63);
-                distinct += __popcll(__ballot(fresh));
-            }
+            u32 distinct;
+            const u32 total = closure_walk<WRITE>(a.tree, TourSeq{a.node_at, seq}, G, lane, dst, distinct);
             if (!WRITE && lane == 0) {
-                a.cnt[rr] = total;
-                atomicAdd(&a.counters[C_ENTRIES], (u64)total);
-                atomicMax(&a.counters[C_LONGEST], (u64)total);
-                if (total == 1) atomicAdd(&a.counters[C_SINGLETONS], 1ull);
+                count_list(a.cnt, a.counters, rr, total);
                 if (total > distinct) atomicAdd(&a.counters[M_GROWN], 1ull);
-                if (total > kMaxList) atomicMax(&a.counters[C_TOOLONG], (u64)total);
-                if (total > 64) { atomicAdd(&a.counters[C_LONG_RUNS], 1ull); atomicAdd(&a.counters[C_LONG_ENTRIES], (u64)total); }
             }
         }
-        if (WRITE && !is_long) {
-            // ascending order within the wave: the entries are distinct, the rank of one is the number of smaller ones
-            wave_sync();
-            const u32 v = lane < n ? s_stage[wv][lane] : 0xFFFFFFFFu;
-            u32 rank = 0;
-            for (u32 t = 0; t < n; ++t) rank += s_stage[wv][t] < v ? 1u : 0u;
-            if (lane < n) a.tids[a.off[rr] + rank] = v;
-            wave_sync();
-        }
+        if (WRITE && n <= 64) rank_store(&s_stage[wv][0], n, lane, a.tids + a.off[rr]);
     }
 }
 
@@ -661,6 +649,48 @@ struct DevBuf {
         return e;
     }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+hipError_t ensure_all(std::initializer_list<std::pair<DevBuf*, size_t>> need) {   // (buffer, bytes) ...
+    for (const auto& n : need)
+        if (const hipError_t e = n.first->ensure(n.second)) return e;
+    return hipSuccess;
+}
+
+// rocPRIM's two calls: without storage it reports the bytes it needs, with them it runs.  call(void* storage, size_t& bytes)
+template <class Call> hipError_t with_temp(DevBuf& temp, Call call) {
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e == hipSuccess) e = temp.ensure(bytes);
+    if (e == hipSuccess) e = call(temp.p, bytes);
+    return e;
+}
+
+// HIP-event time on the stream, stage by stage: lap() adds the ms since start() or the lap before it
+struct LapTimer {
+    hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~LapTimer() { if (ev[0]) hipEventDestroy(ev[0]); if (ev[1]) hipEventDestroy(ev[1]); }
+    hipError_t init(hipStream_t s) {
+        st = s;
+        const hipError_t e = hipEventCreate(&ev[0]);
+        return e == hipSuccess ? hipEventCreate(&ev[1]) : e;
+    }
+    hipError_t start() { return hipEventRecord(ev[0], st); }
+    hipError_t lap(float& acc) {
+        hipError_t e = hipEventRecord(ev[1], st);
+        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        acc += ms;
+        if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+        return e;
+    }
+};
+
+struct LongBufs {   // the side buffers of the lists beyond 64 entries
+    DevBuf tmp, sorted, begin, end, run;
+    LongArgs args() const { return LongArgs{tmp.as<u32>(), begin.as<u32>(), end.as<u32>(), run.as<u32>()}; }
 };
 
 }  // namespace
@@ -854,6 +884,23 @@ int parse_taxhisto(lmat_build* b, const char* fn, lmat_build::Input& in) {
     return LMAT_OK;
 }
 
+// The result in the file format: KmerFileMetaData.cpp:16-31 with tax_histo's version; lists are written in ascending taxid order (the
+// reference writes them in unordered_map iteration order; readers do not rely on either).  False when a write failed.
+bool write_records(FILE* f, const lmat_build* b) {
+    const uint32_t data_start = 29, version = 999, klen = (uint32_t)b->k;
+    const uint64_t count = b->kmers.size(), sanity = ~0ull;
+    const char loc = 'N';
+    bool ok = fwrite(&data_start, 4, 1, f) == 1 && fwrite(&count, 8, 1, f) == 1 && fwrite(&sanity, 8, 1, f) == 1 &&
+              fwrite(&version, 4, 1, f) == 1 && fwrite(&loc, 1, 1, f) == 1 && fwrite(&klen, 4, 1, f) == 1;
+    for (u64 i = 0; i < count && ok; ++i) {
+        const u64 n = b->list_off[i + 1] - b->list_off[i];
+        const uint16_t n16 = (uint16_t)n;
+        ok = fwrite(&b->kmers[i], 8, 1, f) == 1 && fwrite(&n16, 2, 1, f) == 1 && fwrite(&b->tids[b->list_off[i]], 4, n, f) == n;
+        if (ok && (i + 1) % 1500 == 0) ok = fwrite(&sanity, 8, 1, f) == 1;
+    }
+    return ok;
+}
+
 }  // namespace
 
 extern "C" {
@@ -988,19 +1035,7 @@ int lmat_build_write_taxhisto(lmat_build* b, const char* fn) {
     if (!b->done) return berr(b, LMAT_E_ARG, "lmat_build_run first");
     FILE* f = fopen(fn, "wb");
     if (!f) return berr(b, LMAT_E_IO, std::string("cannot open ") + fn + " for writing");
-    // KmerFileMetaData.cpp:16-31 with tax_histo's version; lists are written in ascending taxid order (the reference writes
-    // them in unordered_map iteration order; readers do not rely on either)
-    const uint32_t data_start = 29, version = 999, klen = (uint32_t)b->k;
-    const uint64_t count = b->kmers.size(), sanity = ~0ull;
-    const char loc = 'N';
-    bool ok = fwrite(&data_start, 4, 1, f) == 1 && fwrite(&count, 8, 1, f) == 1 && fwrite(&sanity, 8, 1, f) == 1 &&
-              fwrite(&version, 4, 1, f) == 1 && fwrite(&loc, 1, 1, f) == 1 && fwrite(&klen, 4, 1, f) == 1;
-    for (u64 i = 0; i < count && ok; ++i) {
-        const u64 n = b->list_off[i + 1] - b->list_off[i];
-        const uint16_t n16 = (uint16_t)n;
-        ok = fwrite(&b->kmers[i], 8, 1, f) == 1 && fwrite(&n16, 2, 1, f) == 1 && fwrite(&b->tids[b->list_off[i]], 4, n, f) == n;
-        if (ok && (i + 1) % 1500 == 0) ok = fwrite(&sanity, 8, 1, f) == 1;
-    }
+    bool ok = write_records(f, b);
     if (fclose(f) != 0) ok = false;
     return ok ? LMAT_OK : berr(b, LMAT_E_IO, std::string("write error on ") + fn);
 }
@@ -1047,39 +1082,62 @@ u64 merge_need(const lmat_build* b, int pb, bool& too_many) {
     return need;
 }
 
+// The tail the build and the merge share, count -> CSR: the counts scanned to offsets, the pass's counters read (n_counters words into hc), the
+// list buffer and the side buffers of the lists beyond 64 entries sized exactly, the write pass launched (launch_write(off, tids, long buffers)
+// enqueues it), the long lists ordered by segment and copied into place.  Leaves R + 1 offsets in off and hc[C_ENTRIES] taxids in out.
+template <class Launch>
+int write_lists(lmat_build* b, hipStream_t st, const char* what, u32 R, u64* cnt, u64* off, u64* counters, u64* hc, size_t n_counters, DevBuf& out,
+                LongBufs& lg, DevBuf& temp, Launch launch_write) {
+    BHIP(b, with_temp(temp, [&](void* t, size_t& tb) { return rocprim::exclusive_scan(t, tb, cnt, off, 0ull, (size_t)R, rocprim::plus<u64>(), st); }));
+    BHIP(b, hipMemcpyAsync(hc, counters, n_counters * 8, hipMemcpyDeviceToHost, st));
+    BHIP(b, hipStreamSynchronize(st));
+    if (hc[C_TOOLONG])
+        return berr(b, LMAT_E_CAPACITY, std::string("a ") + what + " of " + std::to_string(hc[C_TOOLONG]) + " entries: the tax_histo record holds at most 65535");
+    const u64 entries = hc[C_ENTRIES], n_long = hc[C_LONG_RUNS], long_entries = hc[C_LONG_ENTRIES];
+    if (long_entries > 0xFFFFFFF0ull) return berr(b, LMAT_E_CAPACITY, "more than 2^32 entries in lists beyond 64 taxids in one pass: raise prefix_bits");
+    BHIP(b, hipMemcpyAsync(off + R, &hc[C_ENTRIES], 8, hipMemcpyHostToDevice, st));
+    BHIP(b, out.ensure(entries * 4));
+    if (n_long) BHIP(b, ensure_all({{&lg.tmp, long_entries * 4}, {&lg.sorted, long_entries * 4}, {&lg.begin, n_long * 4}, {&lg.end, n_long * 4}, {&lg.run, n_long * 4}}));
+    // the write pass hands out the long lists' places with the two counters the count pass filled
+    BHIP(b, hipMemsetAsync(counters + C_LONG_RUNS, 0, 16, st));
+    BHIP(b, launch_write(off, out.as<u32>(), lg.args()));
+    if (n_long) {
+        BHIP(b, with_temp(temp, [&](void* t, size_t& tb) {
+            return rocprim::segmented_radix_sort_keys(t, tb, lg.tmp.as<u32>(), lg.sorted.as<u32>(), (unsigned)long_entries, (unsigned)n_long, lg.begin.as<u32>(),
+                                                      lg.end.as<u32>(), 0, 32, st);
+        }));
+        hipLaunchKernelGGL(long_copy_kernel, dim3((u32)n_long), dim3(256), 0, st, lg.sorted.as<u32>(), lg.begin.as<u32>(), lg.end.as<u32>(), lg.run.as<u32>(), off,
+                           out.as<u32>());
+        BHIP(b, hipGetLastError());
+    }
+    return LMAT_OK;
+}
+
 // The tail of every pass: the merge with the tax_histo inputs (when there are any) and the per-taxid histogram of the final lists.
 struct MergeState {
     lmat_build* b = nullptr;
     hipStream_t st = nullptr;
+    LapTimer* timer = nullptr;            // the build's: a pass of the merge runs between two of its marks
     bool merging = false;
     int pb = 0, sb = 1;
     std::vector<size_t> cursor;           // next record of every input: the passes ascend, an input's slices follow each other
     std::vector<u32> node_at;
     DevBuf tin, d_node_at, hist, counters, totals, keysA, keysB, valsA, valsB, rec_off, ent, flag, pos, run, cnt, off, aux, big_run, big_begin, big_end,
-        big_tmp, big_sorted, out, out_km, long_tmp, long_sorted, long_begin, long_end, long_run, temp;
-    const u32 *parent = nullptr, *depth = nullptr, *node_tid = nullptr;
+        big_tmp, big_sorted, out, out_km, temp;
+    LongBufs lng;
+    TreeArgs tree = {nullptr, nullptr, nullptr};
     u32 n_nodes = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    u64 hc[M_TOTAL];
     u64 singletons = 0, entries = 0, longest = 0;
-    ~MergeState() { if (ev[0]) hipEventDestroy(ev[0]); if (ev[1]) hipEventDestroy(ev[1]); }
 
-    hipError_t lap(float& acc) {
-        hipError_t e = hipEventRecord(ev[1], st);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        acc += ms;
-        if (e == hipSuccess) e = hipEventRecord(ev[0], st);
-        return e;
-    }
+    int key_bits() const { return 2 * b->k + sb; }
 
-    int begin(lmat_build* b_, int pb_, const u32* d_parent, const u32* d_depth, const u32* d_node_tid) {
+    int begin(lmat_build* b_, int pb_, const TreeArgs& tree_, LapTimer* timer_) {
         b = b_;
         st = b->ctx->stream;
         pb = pb_;
-        parent = d_parent;
-        depth = d_depth;
-        node_tid = d_node_tid;
+        tree = tree_;
+        timer = timer_;
         n_nodes = (u32)b->node_tid.size();
         merging = !b->inputs.empty();
         memset(&b->mstats, 0, sizeof(b->mstats));
@@ -1087,17 +1145,12 @@ struct MergeState {
         BHIP(b, hist.ensure((size_t)n_nodes * 8));
         BHIP(b, hipMemsetAsync(hist.p, 0, (size_t)n_nodes * 8, st));
         if (!merging) return LMAT_OK;
-        BHIP(b, hipEventCreate(&ev[0]));
-        BHIP(b, hipEventCreate(&ev[1]));
         sb = 1;
         while ((1ull << sb) < b->inputs.size() + 1) ++sb;   // the genomes' own result is the source behind the inputs
         cursor.assign(b->inputs.size(), 0);
         node_at.assign(n_nodes, 0);
         for (u32 i = 0; i < n_nodes; ++i) node_at[b->tin[i]] = i;
-        BHIP(b, tin.ensure((size_t)n_nodes * 4));
-        BHIP(b, d_node_at.ensure((size_t)n_nodes * 4));
-        BHIP(b, counters.ensure(M_TOTAL * 8));
-        BHIP(b, totals.ensure(16));
+        BHIP(b, ensure_all({{&tin, (size_t)n_nodes * 4}, {&d_node_at, (size_t)n_nodes * 4}, {&counters, M_TOTAL * 8}, {&totals, 16}}));
         BHIP(b, hipMemcpyAsync(tin.p, b->tin.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, st));
         BHIP(b, hipMemcpyAsync(d_node_at.p, node_at.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, st));
         BHIP(b, hipStreamSynchronize(st));
@@ -1110,14 +1163,14 @@ struct MergeState {
     // the histogram of a finished CSR on the device
     int count_lists(const u32* d_tids, u64 n) {
         if (!n) return LMAT_OK;
-        hipLaunchKernelGGL(hist_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_tids, n, node_tid, n_nodes, hist.as<u64>());
+        hipLaunchKernelGGL(hist_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_tids, n, tree.node_tid, n_nodes, hist.as<u64>());
         BHIP(b, hipGetLastError());
         return LMAT_OK;
     }
 
-    // One prefix pass: the inputs' slices and the genomes' result of the pass (gR runs: k-mer, CSR of ascending taxids, runs without a list
-    // included) -> records appended to the builder's result.
-    int pass(u32 pass_no, u32 gR, const u64* g_kmer, const u64* g_off, const u32* g_tids, u64 g_entries) {
+    // Stage 1: the inputs' slices with the pass's prefix and the genomes' result of the pass as the last source -> one key per record in keysA,
+    // record numbers in valsA, list bounds in rec_off, entries as node indices in ent.  Nr = 0: the pass holds nothing.
+    int upload(u32 pass_no, u32 gR, const u64* g_kmer, const u64* g_off, const u32* g_tids, u64 g_entries, u32& Nr) {
         const int k = b->k;
         const size_t n_in = b->inputs.size();
         std::vector<u64> h_keys;
@@ -1143,78 +1196,66 @@ struct MergeState {
         }
         const u64 Nin = h_keys.size(), Ein = h_ent.size();
         const u64 Nr64 = Nin + gR, Ne64 = Ein + g_entries;
+        Nr = 0;
         if (Nr64 == 0) return LMAT_OK;
         if (Nr64 > 0x7FFFFFFFull || Ne64 > 0xFFFFFF00ull) return berr(b, LMAT_E_CAPACITY, "more than 2^31 records or 2^32 list entries to merge in one prefix pass: raise prefix_bits");
-        const u32 Nr = (u32)Nr64;
-        lmat_merge_stats& M = b->mstats;
+        Nr = (u32)Nr64;
         const u32 slots = (u32)(Ne64 / 65 + 1);   // a side-buffer segment holds more than 64 entries
-        BHIP(b, keysA.ensure((size_t)Nr * 8));
-        BHIP(b, keysB.ensure((size_t)Nr * 8));
-        BHIP(b, valsA.ensure((size_t)Nr * 4));
-        BHIP(b, valsB.ensure((size_t)Nr * 4));
-        BHIP(b, rec_off.ensure(((size_t)Nr + 1) * 4));
-        BHIP(b, ent.ensure((size_t)Ne64 * 4));
-        BHIP(b, flag.ensure((size_t)Nr * 4));
-        BHIP(b, pos.ensure((size_t)Nr * 4));
-        BHIP(b, run.ensure(((size_t)Nr + 1) * 4));
-        BHIP(b, cnt.ensure((size_t)Nr * 8));
-        BHIP(b, off.ensure(((size_t)Nr + 1) * 8));
-        BHIP(b, aux.ensure((size_t)Nr * 4));
-        BHIP(b, out_km.ensure((size_t)Nr * 8));
-        BHIP(b, big_run.ensure((size_t)slots * 4));
-        BHIP(b, big_begin.ensure((size_t)slots * 4));
-        BHIP(b, big_end.ensure((size_t)slots * 4));
+        const size_t n = Nr;
+        BHIP(b, ensure_all({{&keysA, n * 8}, {&keysB, n * 8}, {&valsA, n * 4}, {&valsB, n * 4}, {&rec_off, (n + 1) * 4}, {&ent, (size_t)Ne64 * 4}, {&flag, n * 4},
+                            {&pos, n * 4}, {&run, (n + 1) * 4}, {&cnt, n * 8}, {&off, (n + 1) * 8}, {&aux, n * 4}, {&out_km, n * 8}, {&big_run, (size_t)slots * 4},
+                            {&big_begin, (size_t)slots * 4}, {&big_end, (size_t)slots * 4}}));
         BHIP(b, hipMemsetAsync(counters.p, 0, M_TOTAL * 8, st));
-        BHIP(b, hipEventRecord(ev[0], st));
+        BHIP(b, timer->start());
         if (Nin) BHIP(b, hipMemcpyAsync(keysA.p, h_keys.data(), (size_t)Nin * 8, hipMemcpyHostToDevice, st));
         BHIP(b, hipMemcpyAsync(rec_off.p, h_off.data(), ((size_t)Nin + 1) * 4, hipMemcpyHostToDevice, st));
         if (Ein) BHIP(b, hipMemcpyAsync(ent.p, h_ent.data(), (size_t)Ein * 4, hipMemcpyHostToDevice, st));
-        const int key_bits = 2 * k + sb;
         if (gR) {
-            hipLaunchKernelGGL(genome_source_kernel, dim3((gR + 255) / 256), dim3(256), 0, st, gR, g_kmer, g_off, (u32)Nin, (u32)Ein, (u32)n_in, sb, key_bits,
+            hipLaunchKernelGGL(genome_source_kernel, dim3((gR + 255) / 256), dim3(256), 0, st, gR, g_kmer, g_off, (u32)Nin, (u32)Ein, (u32)n_in, sb, key_bits(),
                                keysA.as<u64>(), rec_off.as<u32>(), counters.as<u64>());
             BHIP(b, hipGetLastError());
             if (g_entries) {
-                hipLaunchKernelGGL(tid_to_node_kernel, dim3((u32)((g_entries + 255) / 256)), dim3(256), 0, st, g_tids, g_entries, node_tid, n_nodes, ent.as<u32>() + Ein);
+                hipLaunchKernelGGL(tid_to_node_kernel, dim3((u32)((g_entries + 255) / 256)), dim3(256), 0, st, g_tids, g_entries, tree.node_tid, n_nodes,
+                                   ent.as<u32>() + Ein);
                 BHIP(b, hipGetLastError());
             }
         }
         hipLaunchKernelGGL(iota_kernel, dim3((Nr + 255) / 256), dim3(256), 0, st, valsA.as<u32>(), Nr);
         BHIP(b, hipGetLastError());
         BHIP(b, hipStreamSynchronize(st));   // the host vectors go out of use here
-        BHIP(b, lap(M.upload_ms));
+        BHIP(b, timer->lap(b->mstats.upload_ms));
+        return LMAT_OK;
+    }
 
-        // ---- one key per record, sorted by (k-mer, source); records without a list behind all others
-        {
-            size_t tb = 0;
-            BHIP(b, rocprim::radix_sort_pairs(nullptr, tb, keysA.as<u64>(), keysB.as<u64>(), valsA.as<u32>(), valsB.as<u32>(), Nr, 0, key_bits + 1, st));
-            BHIP(b, temp.ensure(tb));
-            BHIP(b, rocprim::radix_sort_pairs(temp.p, tb, keysA.as<u64>(), keysB.as<u64>(), valsA.as<u32>(), valsB.as<u32>(), Nr, 0, key_bits + 1, st));
-        }
-        u64 hc[M_TOTAL];
+    // Stage 2: one key per record, sorted by (k-mer, source) into keysB / valsB, records without a list behind all others and cut off; then the
+    // runs of one k-mer.  R = 0: no record of the pass has a list.
+    int sort_runs(u32 Nr, u32& R) {
+        lmat_merge_stats& M = b->mstats;
+        R = 0;
+        BHIP(b, with_temp(temp, [&](void* t, size_t& tb) {
+            return rocprim::radix_sort_pairs(t, tb, keysA.as<u64>(), keysB.as<u64>(), valsA.as<u32>(), valsB.as<u32>(), Nr, 0, key_bits() + 1, st);
+        }));
         BHIP(b, hipMemcpyAsync(hc, counters.p, M_TOTAL * 8, hipMemcpyDeviceToHost, st));
-        BHIP(b, lap(M.sort_ms));
+        BHIP(b, timer->lap(M.sort_ms));
         const u32 Nv = Nr - (u32)hc[M_EMPTY];
         if (Nv == 0) return LMAT_OK;
-
-        // ---- runs of one k-mer
         const u32 gridN = (Nv + 255) / 256;
         hipLaunchKernelGGL(mseg_flag_kernel, dim3(gridN), dim3(256), 0, st, keysB.as<u64>(), Nv, sb, flag.as<u32>());
         BHIP(b, hipGetLastError());
-        {
-            size_t tb = 0;
-            BHIP(b, rocprim::exclusive_scan(nullptr, tb, flag.as<u32>(), pos.as<u32>(), 0u, (size_t)Nv, rocprim::plus<u32>(), st));
-            BHIP(b, temp.ensure(tb));
-            BHIP(b, rocprim::exclusive_scan(temp.p, tb, flag.as<u32>(), pos.as<u32>(), 0u, (size_t)Nv, rocprim::plus<u32>(), st));
-        }
+        BHIP(b, with_temp(temp, [&](void* t, size_t& tb) {
+            return rocprim::exclusive_scan(t, tb, flag.as<u32>(), pos.as<u32>(), 0u, (size_t)Nv, rocprim::plus<u32>(), st);
+        }));
         hipLaunchKernelGGL(mseg_scatter_kernel, dim3(gridN), dim3(256), 0, st, flag.as<u32>(), pos.as<u32>(), Nv, run.as<u32>(), totals.as<u64>());
         BHIP(b, hipGetLastError());
         u64 tot[2];
         BHIP(b, hipMemcpyAsync(tot, totals.p, 16, hipMemcpyDeviceToHost, st));
-        BHIP(b, lap(M.segment_ms));
-        const u32 R = (u32)tot[0];
+        BHIP(b, timer->lap(M.segment_ms));
+        R = (u32)tot[0];
+        return LMAT_OK;
+    }
 
-        // ---- union: classify, side-buffer segments in tour order, count, scan, write
+    // Stage 3, the union: classify, side-buffer segments in tour order, count, and the shared tail -> the CSR in off / out, the k-mers in out_km
+    int unite(u32 R) {
         UnionArgs ua;
         memset(&ua, 0, sizeof(ua));
         ua.R = R;
@@ -1224,9 +1265,7 @@ struct MergeState {
         ua.ent = ent.as<u32>();
         ua.tin = tin.as<u32>();
         ua.node_at = d_node_at.as<u32>();
-        ua.parent = parent;
-        ua.depth = depth;
-        ua.node_tid = node_tid;
+        ua.tree = tree;
         ua.aux = aux.as<u32>();
         ua.big_run = big_run.as<u32>();
         ua.big_begin = big_begin.as<u32>();
@@ -1239,69 +1278,47 @@ struct MergeState {
         BHIP(b, hipStreamSynchronize(st));
         const u64 n_big = hc[M_BIG_RUNS], big_entries = hc[M_BIG_ENTRIES];
         if (n_big) {
-            BHIP(b, big_tmp.ensure(big_entries * 4));
-            BHIP(b, big_sorted.ensure(big_entries * 4));
+            BHIP(b, ensure_all({{&big_tmp, big_entries * 4}, {&big_sorted, big_entries * 4}}));
             hipLaunchKernelGGL(big_gather_kernel, dim3((u32)n_big), dim3(256), 0, st, ua, big_tmp.as<u32>());
             BHIP(b, hipGetLastError());
-            size_t tb = 0;
-            BHIP(b, rocprim::segmented_radix_sort_keys(nullptr, tb, big_tmp.as<u32>(), big_sorted.as<u32>(), (unsigned)big_entries, (unsigned)n_big,
-                                                       big_begin.as<u32>(), big_end.as<u32>(), 0, 32, st));
-            BHIP(b, temp.ensure(tb));
-            BHIP(b, rocprim::segmented_radix_sort_keys(temp.p, tb, big_tmp.as<u32>(), big_sorted.as<u32>(), (unsigned)big_entries, (unsigned)n_big,
-                                                       big_begin.as<u32>(), big_end.as<u32>(), 0, 32, st));
+            BHIP(b, with_temp(temp, [&](void* t, size_t& tb) {
+                return rocprim::segmented_radix_sort_keys(t, tb, big_tmp.as<u32>(), big_sorted.as<u32>(), (unsigned)big_entries, (unsigned)n_big, big_begin.as<u32>(),
+                                                          big_end.as<u32>(), 0, 32, st);
+            }));
             ua.big_sorted = big_sorted.as<u32>();
         }
         const u32 gridR = (u32)(((u64)R + 64 * kWavesPerBlock - 1) / (64 * kWavesPerBlock));
         hipLaunchKernelGGL(union_kernel<false>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ua);
         BHIP(b, hipGetLastError());
-        {
-            size_t tb = 0;
-            BHIP(b, rocprim::exclusive_scan(nullptr, tb, cnt.as<u64>(), off.as<u64>(), 0ull, (size_t)R, rocprim::plus<u64>(), st));
-            BHIP(b, temp.ensure(tb));
-            BHIP(b, rocprim::exclusive_scan(temp.p, tb, cnt.as<u64>(), off.as<u64>(), 0ull, (size_t)R, rocprim::plus<u64>(), st));
-        }
-        BHIP(b, hipMemcpyAsync(hc, counters.p, M_TOTAL * 8, hipMemcpyDeviceToHost, st));
-        BHIP(b, hipStreamSynchronize(st));
-        if (hc[C_TOOLONG])
-            return berr(b, LMAT_E_CAPACITY, "a merged taxid list of " + std::to_string(hc[C_TOOLONG]) + " entries: the tax_histo record holds at most 65535");
-        const u64 n_entries = hc[C_ENTRIES], n_long = hc[C_LONG_RUNS], long_entries = hc[C_LONG_ENTRIES];
-        if (long_entries > 0xFFFFFFF0ull) return berr(b, LMAT_E_CAPACITY, "more than 2^32 entries in lists beyond 64 taxids in one pass: raise prefix_bits");
-        BHIP(b, hipMemcpyAsync(off.as<u64>() + R, &n_entries, 8, hipMemcpyHostToDevice, st));
-        BHIP(b, out.ensure(n_entries * 4));
-        if (n_long) {
-            BHIP(b, long_tmp.ensure(long_entries * 4));
-            BHIP(b, long_sorted.ensure(long_entries * 4));
-            BHIP(b, long_begin.ensure(n_long * 4));
-            BHIP(b, long_end.ensure(n_long * 4));
-            BHIP(b, long_run.ensure(n_long * 4));
-        }
-        BHIP(b, hipMemsetAsync(counters.as<u64>() + C_LONG_RUNS, 0, 16, st));   // the write pass hands out the long lists' places with them
-        ua.off = off.as<u64>();
-        ua.tids = out.as<u32>();
-        ua.long_tmp = long_tmp.as<u32>();
-        ua.long_begin = long_begin.as<u32>();
-        ua.long_end = long_end.as<u32>();
-        ua.long_run = long_run.as<u32>();
-        hipLaunchKernelGGL(union_kernel<true>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ua);
-        BHIP(b, hipGetLastError());
-        if (n_long) {
-            size_t tb = 0;
-            BHIP(b, rocprim::segmented_radix_sort_keys(nullptr, tb, long_tmp.as<u32>(), long_sorted.as<u32>(), (unsigned)long_entries, (unsigned)n_long,
-                                                       long_begin.as<u32>(), long_end.as<u32>(), 0, 32, st));
-            BHIP(b, temp.ensure(tb));
-            BHIP(b, rocprim::segmented_radix_sort_keys(temp.p, tb, long_tmp.as<u32>(), long_sorted.as<u32>(), (unsigned)long_entries, (unsigned)n_long,
-                                                       long_begin.as<u32>(), long_end.as<u32>(), 0, 32, st));
-            hipLaunchKernelGGL(long_copy_kernel, dim3((u32)n_long), dim3(256), 0, st, long_sorted.as<u32>(), long_begin.as<u32>(), long_end.as<u32>(),
-                               long_run.as<u32>(), off.as<u64>(), out.as<u32>());
-            BHIP(b, hipGetLastError());
-        }
-        const u64 kmask = (1ull << (2 * k)) - 1;
+        const int rc = write_lists(b, st, "merged taxid list", R, cnt.as<u64>(), off.as<u64>(), counters.as<u64>(), hc, M_TOTAL, out, lng, temp,
+                                   [&](const u64* d_off, u32* d_tids, const LongArgs& lg) {
+                                       ua.off = d_off;
+                                       ua.tids = d_tids;
+                                       ua.lng = lg;
+                                       hipLaunchKernelGGL(union_kernel<true>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ua);
+                                       return hipGetLastError();
+                                   });
+        if (rc) return rc;
+        const u64 kmask = (1ull << (2 * b->k)) - 1;
         hipLaunchKernelGGL(mrun_kmer_kernel, dim3((R + 255) / 256), dim3(256), 0, st, keysB.as<u64>(), run.as<u32>(), R, sb, kmask, out_km.as<u64>());
         BHIP(b, hipGetLastError());
-        BHIP(b, lap(M.union_ms));
-        const int rc = count_lists(out.as<u32>(), n_entries);
-        if (rc) return rc;
-        BHIP(b, lap(M.histogram_ms));
+        BHIP(b, timer->lap(b->mstats.union_ms));
+        return LMAT_OK;
+    }
+
+    // One prefix pass: the inputs' slices and the genomes' result of the pass (gR runs: k-mer, CSR of ascending taxids, runs without a list
+    // included) -> records appended to the builder's result.
+    int pass(u32 pass_no, u32 gR, const u64* g_kmer, const u64* g_off, const u32* g_tids, u64 g_entries) {
+        u32 Nr = 0, R = 0;
+        if (const int rc = upload(pass_no, gR, g_kmer, g_off, g_tids, g_entries, Nr)) return rc;
+        if (Nr == 0) return LMAT_OK;
+        if (const int rc = sort_runs(Nr, R)) return rc;
+        if (R == 0) return LMAT_OK;
+        if (const int rc = unite(R)) return rc;
+        lmat_merge_stats& M = b->mstats;
+        const u64 n_entries = hc[C_ENTRIES];
+        if (const int rc = count_lists(out.as<u32>(), n_entries)) return rc;
+        BHIP(b, timer->lap(M.histogram_ms));
 
         // ---- to the host: every run has a list
         std::vector<u64> h_o((size_t)R + 1);
@@ -1327,147 +1344,127 @@ struct MergeState {
     }
 };
 
-int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
-    lmat_ctx* c = b->ctx;
-    hipStream_t st = c->stream;
-    const int k = b->k;
-    lmat_build_stats& S = b->stats;
-    memset(&S, 0, sizeof(S));
-    b->kmers.clear();
-    b->tids.clear();
-    b->list_off.assign(1, 0);
-    S.bases = b->bases;
-    const u64 T = b->text.size();
-    const u32 n_rec = (u32)b->rec_start.size();
-    if (b->rec_start.size() > 0x7FFFFFFFull) return berr(b, LMAT_E_CAPACITY, "more than 2^31 FASTA records");
-    const bool merging = !b->inputs.empty();
-    b->node_counts.assign(b->node_tid.size(), 0);
-    memset(&b->mstats, 0, sizeof(b->mstats));
-    if ((T == 0 || n_rec == 0) && !merging) return LMAT_OK;
+// One run of the build: what the owner numbering and the memory model decide, and the device buffers of its passes.
+struct BuildRun {
+    lmat_build* b = nullptr;
+    hipStream_t st = nullptr;
+    u64 T = 0;                            // bytes of genome text
+    // owners
+    u32 n_rec = 0, n_owner = 0, n_known = 0;
+    int ob = 1;                           // bits of an owner index
+    bool packed = true;                   // one 64-bit key per pair
+    std::vector<u32> rec_owner, owner_node;
+    // memory model
+    u32 chunk = 0;
+    u64 chunk_alloc = 0, cap = 0;
+    int pb = 0;
+    // device
+    DevBuf text, rec_start, d_rec_owner, d_owner_node, parent, depth, node_tid, counters, totals, keysA, keysB, valsA, valsB, flag, pos, dk, downer, run, temp,
+        tids;
+    LongBufs lng;
+    uint8_t* stage = nullptr;             // pinned: one chunk of text on its way up
+    LapTimer timer;
+    u64 hc[C_N];
+    ~BuildRun() { if (stage) hipHostFree(stage); }
+
+    TreeArgs tree() const { return TreeArgs{parent.as<u32>(), depth.as<u32>(), node_tid.as<u32>()}; }
 
     // owners: distinct taxids; the tree's own in Euler-tour order, the others behind them
-    std::vector<u32> owners(b->rec_taxid);
-    std::sort(owners.begin(), owners.end());
-    owners.erase(std::unique(owners.begin(), owners.end()), owners.end());
-    std::vector<std::pair<u64, u32>> order;   // (sort key, taxid)
-    u32 n_known = 0;
-    for (u32 t : owners) {
-        auto it = b->node_of.find(t);
-        if (it != b->node_of.end()) { order.push_back(std::make_pair((u64)b->tin[it->second], t)); ++n_known; }
-        else order.push_back(std::make_pair((1ull << 32) | t, t));
-    }
-    std::sort(order.begin(), order.end());
-    const u32 n_owner = (u32)order.size();
-    std::unordered_map<u32, u32> owner_of;
-    std::vector<u32> owner_node(n_owner, kNoNode);
-    for (u32 i = 0; i < n_owner; ++i) {
-        owner_of[order[i].second] = i;
-        if (i < n_known) owner_node[i] = b->node_of[order[i].second];
-    }
-    std::vector<u32> rec_owner(n_rec);
-    for (u32 r = 0; r < n_rec; ++r) rec_owner[r] = owner_of[b->rec_taxid[r]];
-    int ob = 1;
-    while ((1ull << ob) < n_owner) ++ob;
-    // one 64-bit key when the owner fits behind the k-mer, else (owner, k-mer) pairs sorted twice; LMAT_DBGEN_SORT=pairs forces the latter
-    bool packed = 2 * k + ob <= 64;
-    if (const char* e = getenv("LMAT_DBGEN_SORT")) if (!strcmp(e, "pairs")) packed = false;
-
-    // memory model: everything below is sized by cap, the pairs one pass may emit
-    u64 budget = b->budget;
-    if (!budget) {
-        size_t fr = 0, tot = 0;
-        BHIP(b, hipMemGetInfo(&fr, &tot));
-        budget = fr / 2;
-    }
-    const u32 chunk = T == 0 ? 1024u : b->chunk_bases ? std::max<u32>(b->chunk_bases, 1024) : (1u << 24);   // T == 0: a merge of tax_histo inputs alone
-    const u64 chunk_waves = ((u64)chunk + kSpan - 1) / kSpan;
-    const u64 chunk_alloc = chunk_waves * kSpan + kLead + 64;
-    const u64 fixed = chunk_alloc + (u64)n_rec * 12 + (u64)b->node_tid.size() * 12 + (u64)n_owner * 4 + (64u << 20);   // + sort scratch and slack
-    const u64 per_pair = 8 + 8 + 8 + 8 + 8 + 4 + 4 + (packed ? 0 : 8) + 16;   // keys x2, flag, pos, distinct pair, run start, (vals x2), list entries (estimate)
-    if (budget <= fixed || (budget <= fixed + per_pair * 1024 && T != 0)) return berr(b, LMAT_E_NOMEM, "device budget of " + std::to_string(budget) + " bytes is below the fixed buffers");
-    u64 cap = std::min<u64>((budget - fixed) / per_pair, 0x7FFFFF00ull);
-    int pb = pb_forced;
-    if (pb < 0) {
-        // canonical k-mers crowd the low prefixes (min of a k-mer and its reverse complement): up to twice the even share
-        pb = pb_start;
-        while (pb < std::min(2 * k, 24) && (double)T * 2.0 / (double)(1ull << pb) > (double)cap && T > cap) ++pb;
-        if (pb == 0 && T > cap) pb = 1;
-    }
-    if (merging) {
-        // The slices of the inputs are known exactly; what they take of a pass comes off the budget first, the pairs of the genomes share the rest
-        // with the records and entries their own result adds to the merge (at most one record per pair, lists as the estimate above has them).
-        const u64 avail = budget - fixed;
-        const u64 per_pair_m = per_pair + kMergeRecBytes + 2 * kMergeEntBytes;
-        const int pb_max = std::min(2 * k, 24);
-        for (pb = pb_forced < 0 ? pb_start : pb_forced;; ++pb) {
-            bool too_many = false;
-            const u64 need = merge_need(b, pb, too_many);
-            const bool in_fit = !too_many && need + (T ? per_pair_m * 1024 : 0) < avail;
-            if (in_fit) cap = std::min<u64>((avail - need) / per_pair_m, 0x7FFFFF00ull);
-            const bool seq_fit = in_fit && (T <= cap || (double)T * 2.0 / (double)(1ull << pb) <= (double)cap);
-            if (in_fit && (seq_fit || pb_forced >= 0)) break;   // a forced split that the genomes overflow is found by the extraction, as without inputs
-            if (pb_forced >= 0 || pb >= pb_max)
-                return berr(b, LMAT_E_CAPACITY, "the tax_histo inputs take " + std::to_string(need) + " bytes in one of the " + std::to_string(1ull << pb) +
-                                                   " prefix passes, the device budget leaves " + std::to_string(avail) + ": raise the budget or prefix_bits");
+    void number_owners() {
+        std::vector<u32> owners(b->rec_taxid);
+        std::sort(owners.begin(), owners.end());
+        owners.erase(std::unique(owners.begin(), owners.end()), owners.end());
+        std::vector<std::pair<u64, u32>> order;   // (sort key, taxid)
+        for (u32 t : owners) {
+            auto it = b->node_of.find(t);
+            if (it != b->node_of.end()) { order.push_back(std::make_pair((u64)b->tin[it->second], t)); ++n_known; }
+            else order.push_back(std::make_pair((1ull << 32) | t, t));
         }
+        std::sort(order.begin(), order.end());
+        n_owner = (u32)order.size();
+        std::unordered_map<u32, u32> owner_of;
+        owner_node.assign(n_owner, kNoNode);
+        for (u32 i = 0; i < n_owner; ++i) {
+            owner_of[order[i].second] = i;
+            if (i < n_known) owner_node[i] = b->node_of[order[i].second];
+        }
+        rec_owner.resize(n_rec);
+        for (u32 r = 0; r < n_rec; ++r) rec_owner[r] = owner_of[b->rec_taxid[r]];
+        while ((1ull << ob) < n_owner) ++ob;
+        // one 64-bit key when the owner fits behind the k-mer, else (owner, k-mer) pairs sorted twice; LMAT_DBGEN_SORT=pairs forces the latter
+        packed = 2 * b->k + ob <= 64;
+        if (const char* e = getenv("LMAT_DBGEN_SORT")) if (!strcmp(e, "pairs")) packed = false;
     }
-    cap = std::min<u64>(cap, T);   // no pass emits more pairs than there are bases
-    S.prefix_bits = (uint32_t)pb;
-    S.passes = 1u << pb;
 
-    DevBuf d_text, d_rec_start, d_rec_owner, d_owner_node, d_parent, d_depth, d_node_tid, d_counters, d_keysA, d_keysB, d_valsA, d_valsB,
-        d_flag, d_pos, d_dk, d_do, d_run, d_temp, d_tids, d_long_tmp, d_long_sorted, d_long_begin, d_long_end, d_long_run, d_totals;
-    BHIP(b, d_text.ensure(chunk_alloc));
-    BHIP(b, d_rec_start.ensure((size_t)n_rec * 8));
-    BHIP(b, d_rec_owner.ensure((size_t)n_rec * 4));
-    BHIP(b, d_owner_node.ensure((size_t)n_owner * 4));
-    BHIP(b, d_parent.ensure(b->parent.size() * 4));
-    BHIP(b, d_depth.ensure(b->depth.size() * 4));
-    BHIP(b, d_node_tid.ensure(b->node_tid.size() * 4));
-    BHIP(b, d_counters.ensure(C_N * 8));
-    BHIP(b, d_totals.ensure(16));
-    BHIP(b, d_keysA.ensure(cap * 8));
-    BHIP(b, d_keysB.ensure(cap * 8));
-    if (!packed) { BHIP(b, d_valsA.ensure(cap * 4)); BHIP(b, d_valsB.ensure(cap * 4)); }
-    BHIP(b, d_flag.ensure(cap * 8));
-    BHIP(b, d_pos.ensure(cap * 8));
-    BHIP(b, d_dk.ensure(cap * 8));
-    BHIP(b, d_do.ensure(cap * 4));
-    BHIP(b, d_run.ensure((cap + 1) * 4));
-    if (n_rec) {
-        BHIP(b, hipMemcpyAsync(d_rec_start.p, b->rec_start.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
-        BHIP(b, hipMemcpyAsync(d_rec_owner.p, rec_owner.data(), (size_t)n_rec * 4, hipMemcpyHostToDevice, st));
-        BHIP(b, hipMemcpyAsync(d_owner_node.p, owner_node.data(), (size_t)n_owner * 4, hipMemcpyHostToDevice, st));
+    // memory model: everything on the device is sized by cap, the pairs one pass may emit; prefix_bits is forced or the smallest split that fits
+    int plan(int pb_forced, int pb_start) {
+        const int k = b->k;
+        u64 budget = b->budget;
+        if (!budget) {
+            size_t fr = 0, tot = 0;
+            BHIP(b, hipMemGetInfo(&fr, &tot));
+            budget = fr / 2;
+        }
+        chunk = T == 0 ? 1024u : b->chunk_bases ? std::max<u32>(b->chunk_bases, 1024) : (1u << 24);   // T == 0: a merge of tax_histo inputs alone
+        const u64 chunk_waves = ((u64)chunk + kSpan - 1) / kSpan;
+        chunk_alloc = chunk_waves * kSpan + kLead + 64;
+        const u64 fixed = chunk_alloc + (u64)n_rec * 12 + (u64)b->node_tid.size() * 12 + (u64)n_owner * 4 + (64u << 20);   // + sort scratch and slack
+        const u64 per_pair = 8 + 8 + 8 + 8 + 8 + 4 + 4 + (packed ? 0 : 8) + 16;   // keys x2, flag, pos, distinct pair, run start, (vals x2), list entries (estimate)
+        if (budget <= fixed || (budget <= fixed + per_pair * 1024 && T != 0)) return berr(b, LMAT_E_NOMEM, "device budget of " + std::to_string(budget) + " bytes is below the fixed buffers");
+        cap = std::min<u64>((budget - fixed) / per_pair, 0x7FFFFF00ull);
+        pb = pb_forced;
+        if (pb < 0) {
+            // canonical k-mers crowd the low prefixes (min of a k-mer and its reverse complement): up to twice the even share
+            pb = pb_start;
+            while (pb < std::min(2 * k, 24) && (double)T * 2.0 / (double)(1ull << pb) > (double)cap && T > cap) ++pb;
+            if (pb == 0 && T > cap) pb = 1;
+        }
+        if (!b->inputs.empty()) {
+            // The slices of the inputs are known exactly; what they take of a pass comes off the budget first, the pairs of the genomes share the rest
+            // with the records and entries their own result adds to the merge (at most one record per pair, lists as the estimate above has them).
+            const u64 avail = budget - fixed;
+            const u64 per_pair_m = per_pair + kMergeRecBytes + 2 * kMergeEntBytes;
+            const int pb_max = std::min(2 * k, 24);
+            for (pb = pb_forced < 0 ? pb_start : pb_forced;; ++pb) {
+                bool too_many = false;
+                const u64 need = merge_need(b, pb, too_many);
+                const bool in_fit = !too_many && need + (T ? per_pair_m * 1024 : 0) < avail;
+                if (in_fit) cap = std::min<u64>((avail - need) / per_pair_m, 0x7FFFFF00ull);
+                const bool seq_fit = in_fit && (T <= cap || (double)T * 2.0 / (double)(1ull << pb) <= (double)cap);
+                if (in_fit && (seq_fit || pb_forced >= 0)) break;   // a forced split that the genomes overflow is found by the extraction, as without inputs
+                if (pb_forced >= 0 || pb >= pb_max)
+                    return berr(b, LMAT_E_CAPACITY, "the tax_histo inputs take " + std::to_string(need) + " bytes in one of the " + std::to_string(1ull << pb) +
+                                                       " prefix passes, the device budget leaves " + std::to_string(avail) + ": raise the budget or prefix_bits");
+            }
+        }
+        cap = std::min<u64>(cap, T);   // no pass emits more pairs than there are bases
+        return LMAT_OK;
     }
-    BHIP(b, hipMemcpyAsync(d_parent.p, b->parent.data(), b->parent.size() * 4, hipMemcpyHostToDevice, st));
-    BHIP(b, hipMemcpyAsync(d_depth.p, b->depth.data(), b->depth.size() * 4, hipMemcpyHostToDevice, st));
-    BHIP(b, hipMemcpyAsync(d_node_tid.p, b->node_tid.data(), b->node_tid.size() * 4, hipMemcpyHostToDevice, st));
-    BHIP(b, hipStreamSynchronize(st));
-    uint8_t* stage = nullptr;
-    BHIP(b, hipHostMalloc((void**)&stage, chunk_alloc));
-    struct StageFree { uint8_t* p; ~StageFree() { hipHostFree(p); } } stage_free{stage};
-    hipEvent_t ev[2];
-    BHIP(b, hipEventCreate(&ev[0]));
-    BHIP(b, hipEventCreate(&ev[1]));
-    struct EvFree { hipEvent_t* e; ~EvFree() { hipEventDestroy(e[0]); hipEventDestroy(e[1]); } } ev_free{ev};
-    auto lap = [&](float& acc) -> hipError_t {   // time on the stream since the last mark
-        hipError_t e = hipEventRecord(ev[1], st);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        acc += ms;
-        if (e == hipSuccess) e = hipEventRecord(ev[0], st);
-        return e;
-    };
 
-    // the per-taxid histogram of the final lists, and the merge with the tax_histo inputs when there are any
-    MergeState tail;
-    if (const int rc = tail.begin(b, pb, d_parent.as<u32>(), d_depth.as<u32>(), d_node_tid.as<u32>())) return rc;
+    // the buffers of a pass, the records, the owners and the tree on the device
+    int alloc() {
+        BHIP(b, ensure_all({{&text, chunk_alloc}, {&rec_start, (size_t)n_rec * 8}, {&d_rec_owner, (size_t)n_rec * 4}, {&d_owner_node, (size_t)n_owner * 4},
+                            {&parent, b->parent.size() * 4}, {&depth, b->depth.size() * 4}, {&node_tid, b->node_tid.size() * 4}, {&counters, C_N * 8}, {&totals, 16},
+                            {&keysA, cap * 8}, {&keysB, cap * 8}, {&flag, cap * 8}, {&pos, cap * 8}, {&dk, cap * 8}, {&downer, cap * 4}, {&run, (cap + 1) * 4}}));
+        if (!packed) BHIP(b, ensure_all({{&valsA, cap * 4}, {&valsB, cap * 4}}));
+        if (n_rec) {
+            BHIP(b, hipMemcpyAsync(rec_start.p, b->rec_start.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
+            BHIP(b, hipMemcpyAsync(d_rec_owner.p, rec_owner.data(), (size_t)n_rec * 4, hipMemcpyHostToDevice, st));
+            BHIP(b, hipMemcpyAsync(d_owner_node.p, owner_node.data(), (size_t)n_owner * 4, hipMemcpyHostToDevice, st));
+        }
+        BHIP(b, hipMemcpyAsync(parent.p, b->parent.data(), b->parent.size() * 4, hipMemcpyHostToDevice, st));
+        BHIP(b, hipMemcpyAsync(depth.p, b->depth.data(), b->depth.size() * 4, hipMemcpyHostToDevice, st));
+        BHIP(b, hipMemcpyAsync(node_tid.p, b->node_tid.data(), b->node_tid.size() * 4, hipMemcpyHostToDevice, st));
+        BHIP(b, hipStreamSynchronize(st));
+        BHIP(b, hipHostMalloc((void**)&stage, chunk_alloc));
+        BHIP(b, timer.init(st));
+        return LMAT_OK;
+    }
 
-    u64 host_c[C_N];
-    for (u32 pass = 0; pass < (1u << pb); ++pass) {
-        BHIP(b, hipMemsetAsync(d_counters.p, 0, C_N * 8, st));
-        BHIP(b, hipEventRecord(ev[0], st));
+    // the pairs of one prefix pass into keysA (valsA); the pass's counters into hc
+    int extract(u32 pass) {
+        BHIP(b, hipMemsetAsync(counters.p, 0, C_N * 8, st));
+        BHIP(b, timer.start());
         for (u64 lo = 0; lo < T; lo += chunk) {
             const u32 len = (u32)std::min<u64>(chunk, T - lo);
             const u64 waves = ((u64)len + kSpan - 1) / kSpan;
@@ -1478,173 +1475,177 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
             const u64 avail = std::min<u64>(T - lo, bytes - kLead);   // bases behind the chunk's end are read but never end a window of it
             memcpy(stage + kLead, b->text.data() + lo, avail);
             memset(stage + kLead + avail, 'N', bytes - kLead - avail);
-            BHIP(b, hipMemcpyAsync(d_text.p, stage, bytes, hipMemcpyHostToDevice, st));
+            BHIP(b, hipMemcpyAsync(text.p, stage, bytes, hipMemcpyHostToDevice, st));
             ExtractArgs a;
-            a.buf = d_text.as<uint8_t>();
+            a.buf = text.as<uint8_t>();
             a.chunk_lo = lo;
             a.chunk_len = len;
-            a.rec_start = d_rec_start.as<u64>();
+            a.rec_start = rec_start.as<u64>();
             a.rec_owner = d_rec_owner.as<u32>();
             a.n_rec = n_rec;
-            a.k = k;
+            a.k = b->k;
             a.prefix_bits = pb;
             a.owner_bits = packed ? ob : -1;
             a.pass = pass;
-            a.keys = d_keysA.as<u64>();
-            a.vals = d_valsA.as<u32>();
+            a.keys = keysA.as<u64>();
+            a.vals = valsA.as<u32>();
             a.cap = cap;
-            a.counters = d_counters.as<u64>();
+            a.counters = counters.as<u64>();
             const u32 grid = (u32)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
             hipLaunchKernelGGL(extract_kernel, dim3(grid), dim3(64 * kWavesPerBlock), 0, st, a);
             BHIP(b, hipGetLastError());
             BHIP(b, hipStreamSynchronize(st));   // the staging buffer is refilled next
         }
-        BHIP(b, lap(S.extract_ms));
-        BHIP(b, hipMemcpy(host_c, d_counters.p, C_N * 8, hipMemcpyDeviceToHost));
-        if (host_c[C_OVERFLOW]) {
-            if (pb_forced < 0) { retry = true; return berr(b, LMAT_E_CAPACITY, "pass buffer too small"); }
-            return berr(b, LMAT_E_CAPACITY, "prefix pass " + std::to_string(pass) + " of " + std::to_string(1u << pb) + " emits " + std::to_string(host_c[C_CURSOR]) +
-                                               " pairs, the device budget holds " + std::to_string(cap) + ": raise the budget or prefix_bits");
-        }
-        const u64 N = host_c[C_CURSOR];
-        if (pass == 0) S.windows = host_c[C_WINDOWS];   // every pass sees every window; only the emitted pairs differ
-        S.emitted_pairs += N;
-        if (N == 0) {
-            if (merging) if (const int rc = tail.pass(pass, 0, nullptr, nullptr, nullptr, 0)) return rc;
-            continue;
-        }
+        BHIP(b, timer.lap(b->stats.extract_ms));
+        BHIP(b, hipMemcpy(hc, counters.p, C_N * 8, hipMemcpyDeviceToHost));
+        return LMAT_OK;
+    }
 
+    // The N pairs of a pass -> its R runs: the k-mers in pos, the CSR of ascending taxids in *off_buf (R + 1 offsets) and tids (hc[C_ENTRIES]).
+    int lists(u64 N, u32& R, DevBuf*& off_buf) {
+        const int k = b->k;
+        lmat_build_stats& S = b->stats;
         // ---- sort by (k-mer, owner)
         Sorted sorted;
         sorted.owner_bits = packed ? ob : -1;
         if (packed) {
-            size_t tb = 0;
-            BHIP(b, rocprim::radix_sort_keys(nullptr, tb, d_keysA.as<u64>(), d_keysB.as<u64>(), N, 0, 2 * k + ob, st));
-            BHIP(b, d_temp.ensure(tb));
-            BHIP(b, rocprim::radix_sort_keys(d_temp.p, tb, d_keysA.as<u64>(), d_keysB.as<u64>(), N, 0, 2 * k + ob, st));
-            sorted.keys = d_keysB.as<u64>();
+            BHIP(b, with_temp(temp, [&](void* t, size_t& tb) { return rocprim::radix_sort_keys(t, tb, keysA.as<u64>(), keysB.as<u64>(), N, 0, 2 * k + ob, st); }));
+            sorted.keys = keysB.as<u64>();
             sorted.vals = nullptr;
         } else {
-            size_t tb1 = 0, tb2 = 0;
-            BHIP(b, rocprim::radix_sort_pairs(nullptr, tb1, d_valsA.as<u32>(), d_valsB.as<u32>(), d_keysA.as<u64>(), d_keysB.as<u64>(), N, 0, ob, st));
-            BHIP(b, rocprim::radix_sort_pairs(nullptr, tb2, d_keysB.as<u64>(), d_keysA.as<u64>(), d_valsB.as<u32>(), d_valsA.as<u32>(), N, 0, 2 * k, st));
-            BHIP(b, d_temp.ensure(std::max(tb1, tb2)));
-            BHIP(b, rocprim::radix_sort_pairs(d_temp.p, tb1, d_valsA.as<u32>(), d_valsB.as<u32>(), d_keysA.as<u64>(), d_keysB.as<u64>(), N, 0, ob, st));
-            BHIP(b, rocprim::radix_sort_pairs(d_temp.p, tb2, d_keysB.as<u64>(), d_keysA.as<u64>(), d_valsB.as<u32>(), d_valsA.as<u32>(), N, 0, 2 * k, st));
-            sorted.keys = d_keysA.as<u64>();
-            sorted.vals = d_valsA.as<u32>();
+            BHIP(b, with_temp(temp, [&](void* t, size_t& tb) {   // by owner, then -- stable -- by k-mer: one storage for both
+                size_t tb1 = tb, tb2 = tb;
+                hipError_t e = rocprim::radix_sort_pairs(t, tb1, valsA.as<u32>(), valsB.as<u32>(), keysA.as<u64>(), keysB.as<u64>(), N, 0, ob, st);
+                if (e == hipSuccess) e = rocprim::radix_sort_pairs(t, tb2, keysB.as<u64>(), keysA.as<u64>(), valsB.as<u32>(), valsA.as<u32>(), N, 0, 2 * k, st);
+                tb = std::max(tb1, tb2);
+                return e;
+            }));
+            sorted.keys = keysA.as<u64>();
+            sorted.vals = valsA.as<u32>();
         }
-        BHIP(b, lap(S.sort_ms));
+        BHIP(b, timer.lap(S.sort_ms));
 
         // ---- distinct pairs and run heads
         const u32 gridN = (u32)((N + 255) / 256);
-        hipLaunchKernelGGL(seg_flag_kernel, dim3(gridN), dim3(256), 0, st, sorted, N, d_flag.as<u64>());
+        hipLaunchKernelGGL(seg_flag_kernel, dim3(gridN), dim3(256), 0, st, sorted, N, flag.as<u64>());
         BHIP(b, hipGetLastError());
-        {
-            size_t tb = 0;
-            BHIP(b, rocprim::exclusive_scan(nullptr, tb, d_flag.as<u64>(), d_pos.as<u64>(), 0ull, N, rocprim::plus<u64>(), st));
-            BHIP(b, d_temp.ensure(tb));
-            BHIP(b, rocprim::exclusive_scan(d_temp.p, tb, d_flag.as<u64>(), d_pos.as<u64>(), 0ull, N, rocprim::plus<u64>(), st));
-        }
-        hipLaunchKernelGGL(seg_scatter_kernel, dim3(gridN), dim3(256), 0, st, sorted, N, d_flag.as<u64>(), d_pos.as<u64>(), d_dk.as<u64>(), d_do.as<u32>(),
-                           d_run.as<u32>(), d_totals.as<u64>());
+        BHIP(b, with_temp(temp, [&](void* t, size_t& tb) { return rocprim::exclusive_scan(t, tb, flag.as<u64>(), pos.as<u64>(), 0ull, N, rocprim::plus<u64>(), st); }));
+        hipLaunchKernelGGL(seg_scatter_kernel, dim3(gridN), dim3(256), 0, st, sorted, N, flag.as<u64>(), pos.as<u64>(), dk.as<u64>(), downer.as<u32>(), run.as<u32>(),
+                           totals.as<u64>());
         BHIP(b, hipGetLastError());
-        u64 totals[2];
-        BHIP(b, hipMemcpyAsync(totals, d_totals.p, 16, hipMemcpyDeviceToHost, st));
-        BHIP(b, lap(S.segment_ms));
-        const u32 R = (u32)totals[1];
+        u64 tot[2];
+        BHIP(b, hipMemcpyAsync(tot, totals.p, 16, hipMemcpyDeviceToHost, st));
+        BHIP(b, timer.lap(S.segment_ms));
+        R = (u32)tot[1];
         S.distinct_kmers += R;
 
-        // ---- closure: count, scan, write.  cnt reuses the flag array, off the scan's output (both are R + 1 <= N + 1 long at most: cap + 1 was not
-        // allocated for them, so the last offset is kept on the host)
+        // ---- closure: count, then the shared tail.  cnt reuses the flag array, off a key buffer (both are R + 1 <= N + 1 long at most)
         ClosureArgs ca;
         memset(&ca, 0, sizeof(ca));
         ca.R = R;
-        ca.run_start = d_run.as<u32>();
-        ca.d_owner = d_do.as<u32>();
+        ca.run_start = run.as<u32>();
+        ca.d_owner = downer.as<u32>();
         ca.n_known = n_known;
         ca.owner_node = d_owner_node.as<u32>();
-        ca.parent = d_parent.as<u32>();
-        ca.depth = d_depth.as<u32>();
-        ca.node_tid = d_node_tid.as<u32>();
-        ca.cnt = d_flag.as<u64>();
-        ca.counters = d_counters.as<u64>();
+        ca.tree = tree();
+        ca.cnt = flag.as<u64>();
+        ca.counters = counters.as<u64>();
         const u32 gridR = (u32)(((u64)R + 64 * kWavesPerBlock - 1) / (64 * kWavesPerBlock));
         hipLaunchKernelGGL(closure_kernel<false>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ca);
         BHIP(b, hipGetLastError());
         // offsets: R + 1 entries in a buffer of their own size class (keysA is free once the pairs are sorted and scattered ... unless it holds them)
-        DevBuf& d_off = packed ? d_keysA : d_keysB;
-        if ((u64)R + 1 > cap) BHIP(b, d_off.ensure(((u64)R + 1) * 8));
-        {
-            size_t tb = 0;
-            BHIP(b, rocprim::exclusive_scan(nullptr, tb, d_flag.as<u64>(), d_off.as<u64>(), 0ull, (size_t)R, rocprim::plus<u64>(), st));
-            BHIP(b, d_temp.ensure(tb));
-            BHIP(b, rocprim::exclusive_scan(d_temp.p, tb, d_flag.as<u64>(), d_off.as<u64>(), 0ull, (size_t)R, rocprim::plus<u64>(), st));
-        }
-        BHIP(b, hipMemcpyAsync(host_c, d_counters.p, C_N * 8, hipMemcpyDeviceToHost, st));
-        BHIP(b, hipStreamSynchronize(st));
-        if (host_c[C_TOOLONG])
-            return berr(b, LMAT_E_CAPACITY, "a taxid list of " + std::to_string(host_c[C_TOOLONG]) + " entries: the tax_histo record holds at most 65535");
-        const u64 entries = host_c[C_ENTRIES];
-        const u64 n_long = host_c[C_LONG_RUNS], long_entries = host_c[C_LONG_ENTRIES];
-        if (long_entries > 0xFFFFFFF0ull) return berr(b, LMAT_E_CAPACITY, "more than 2^32 entries in lists beyond 64 taxids in one pass: raise prefix_bits");
-        BHIP(b, hipMemcpyAsync(d_off.as<u64>() + R, &entries, 8, hipMemcpyHostToDevice, st));
-        BHIP(b, d_tids.ensure(entries * 4));
-        if (n_long) {
-            BHIP(b, d_long_tmp.ensure(long_entries * 4));
-            BHIP(b, d_long_sorted.ensure(long_entries * 4));
-            BHIP(b, d_long_begin.ensure(n_long * 4));
-            BHIP(b, d_long_end.ensure(n_long * 4));
-            BHIP(b, d_long_run.ensure(n_long * 4));
-        }
-        // the write pass hands out the long lists' places with the two counters the count pass filled
-        BHIP(b, hipMemsetAsync(d_counters.as<u64>() + C_LONG_RUNS, 0, 16, st));
-        ca.off = d_off.as<u64>();
-        ca.tids = d_tids.as<u32>();
-        ca.long_tmp = d_long_tmp.as<u32>();
-        ca.long_begin = d_long_begin.as<u32>();
-        ca.long_end = d_long_end.as<u32>();
-        ca.long_run = d_long_run.as<u32>();
-        hipLaunchKernelGGL(closure_kernel<true>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ca);
-        BHIP(b, hipGetLastError());
-        if (n_long) {
-            size_t tb = 0;
-            BHIP(b, rocprim::segmented_radix_sort_keys(nullptr, tb, d_long_tmp.as<u32>(), d_long_sorted.as<u32>(), (unsigned)long_entries, (unsigned)n_long,
-                                                       d_long_begin.as<u32>(), d_long_end.as<u32>(), 0, 32, st));
-            BHIP(b, d_temp.ensure(tb));
-            BHIP(b, rocprim::segmented_radix_sort_keys(d_temp.p, tb, d_long_tmp.as<u32>(), d_long_sorted.as<u32>(), (unsigned)long_entries, (unsigned)n_long,
-                                                       d_long_begin.as<u32>(), d_long_end.as<u32>(), 0, 32, st));
-            hipLaunchKernelGGL(long_copy_kernel, dim3((u32)n_long), dim3(256), 0, st, d_long_sorted.as<u32>(), d_long_begin.as<u32>(), d_long_end.as<u32>(),
-                               d_long_run.as<u32>(), d_off.as<u64>(), d_tids.as<u32>());
-            BHIP(b, hipGetLastError());
-        }
+        off_buf = packed ? &keysA : &keysB;
+        if ((u64)R + 1 > cap) BHIP(b, off_buf->ensure(((u64)R + 1) * 8));
+        const int rc = write_lists(b, st, "taxid list", R, flag.as<u64>(), off_buf->as<u64>(), counters.as<u64>(), hc, C_N, tids, lng, temp,
+                                   [&](const u64* d_off, u32* d_tids, const LongArgs& lg) {
+                                       ca.off = d_off;
+                                       ca.tids = d_tids;
+                                       ca.lng = lg;
+                                       hipLaunchKernelGGL(closure_kernel<true>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ca);
+                                       return hipGetLastError();
+                                   });
+        if (rc) return rc;
         // the k-mer of every run, into the scan's old output
-        hipLaunchKernelGGL(run_kmer_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d_dk.as<u64>(), d_run.as<u32>(), R, d_pos.as<u64>());
+        hipLaunchKernelGGL(run_kmer_kernel, dim3((R + 255) / 256), dim3(256), 0, st, dk.as<u64>(), run.as<u32>(), R, pos.as<u64>());
         BHIP(b, hipGetLastError());
-        BHIP(b, lap(S.closure_ms));
-        if (merging) {   // the pass's result stays on the device and is one more source of the merge
-            if (const int rc = tail.pass(pass, R, d_pos.as<u64>(), d_off.as<u64>(), d_tids.as<u32>(), entries)) return rc;
-            S.dropped_unknown += host_c[C_DROPPED];
-            continue;
-        }
-        if (const int rc = tail.count_lists(d_tids.as<u32>(), entries)) return rc;
+        BHIP(b, timer.lap(S.closure_ms));
+        return LMAT_OK;
+    }
 
-        // ---- to the host: records without a known owner are left out (tax_histo.cpp:239-248)
+    // the pass's records to the host: those without a known owner are left out (tax_histo.cpp:239-248)
+    int fetch(u32 R, const DevBuf& off_buf) {
+        const u64 entries = hc[C_ENTRIES];
         std::vector<u64> h_km(R), h_off((size_t)R + 1);
         const size_t t0 = b->tids.size();
         b->tids.resize(t0 + entries);
-        BHIP(b, hipMemcpy(h_km.data(), d_pos.p, (size_t)R * 8, hipMemcpyDeviceToHost));
-        BHIP(b, hipMemcpy(h_off.data(), d_off.p, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost));
-        if (entries) BHIP(b, hipMemcpy(b->tids.data() + t0, d_tids.p, entries * 4, hipMemcpyDeviceToHost));
+        BHIP(b, hipMemcpy(h_km.data(), pos.p, (size_t)R * 8, hipMemcpyDeviceToHost));
+        BHIP(b, hipMemcpy(h_off.data(), off_buf.p, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost));
+        if (entries) BHIP(b, hipMemcpy(b->tids.data() + t0, tids.p, entries * 4, hipMemcpyDeviceToHost));
         for (u32 r = 0; r < R; ++r) {
             if (h_off[r + 1] == h_off[r]) continue;
             b->kmers.push_back(h_km[r]);
             b->list_off.push_back(t0 + h_off[r + 1]);
         }
-        S.dropped_unknown += host_c[C_DROPPED];
-        S.singletons += host_c[C_SINGLETONS];
+        return LMAT_OK;
+    }
+};
+
+int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
+    lmat_build_stats& S = b->stats;
+    memset(&S, 0, sizeof(S));
+    b->kmers.clear();
+    b->tids.clear();
+    b->list_off.assign(1, 0);
+    S.bases = b->bases;
+    if (b->rec_start.size() > 0x7FFFFFFFull) return berr(b, LMAT_E_CAPACITY, "more than 2^31 FASTA records");
+    const bool merging = !b->inputs.empty();
+    b->node_counts.assign(b->node_tid.size(), 0);
+    memset(&b->mstats, 0, sizeof(b->mstats));
+    BuildRun r;
+    r.b = b;
+    r.st = b->ctx->stream;
+    r.T = b->text.size();
+    r.n_rec = (u32)b->rec_start.size();
+    if ((r.T == 0 || r.n_rec == 0) && !merging) return LMAT_OK;
+    r.number_owners();
+    if (const int rc = r.plan(pb_forced, pb_start)) return rc;
+    const int pb = r.pb;
+    S.prefix_bits = (uint32_t)pb;
+    S.passes = 1u << pb;
+    if (const int rc = r.alloc()) return rc;
+
+    // the per-taxid histogram of the final lists, and the merge with the tax_histo inputs when there are any
+    MergeState tail;
+    if (const int rc = tail.begin(b, pb, r.tree(), &r.timer)) return rc;
+
+    for (u32 pass = 0; pass < (1u << pb); ++pass) {
+        if (const int rc = r.extract(pass)) return rc;
+        if (r.hc[C_OVERFLOW]) {
+            if (pb_forced < 0) { retry = true; return berr(b, LMAT_E_CAPACITY, "pass buffer too small"); }
+            return berr(b, LMAT_E_CAPACITY, "prefix pass " + std::to_string(pass) + " of " + std::to_string(1u << pb) + " emits " + std::to_string(r.hc[C_CURSOR]) +
+                                               " pairs, the device budget holds " + std::to_string(r.cap) + ": raise the budget or prefix_bits");
+        }
+        const u64 N = r.hc[C_CURSOR];
+        if (pass == 0) S.windows = r.hc[C_WINDOWS];   // every pass sees every window; only the emitted pairs differ
+        S.emitted_pairs += N;
+        if (N == 0) {
+            if (merging) if (const int rc = tail.pass(pass, 0, nullptr, nullptr, nullptr, 0)) return rc;
+            continue;
+        }
+        u32 R = 0;
+        DevBuf* off = nullptr;
+        if (const int rc = r.lists(N, R, off)) return rc;
+        const u64 entries = r.hc[C_ENTRIES];
+        S.dropped_unknown += r.hc[C_DROPPED];
+        if (merging) {   // the pass's result stays on the device and is one more source of the merge
+            if (const int rc = tail.pass(pass, R, r.pos.as<u64>(), off->as<u64>(), r.tids.as<u32>(), entries)) return rc;
+            continue;
+        }
+        if (const int rc = tail.count_lists(r.tids.as<u32>(), entries)) return rc;
+        if (const int rc = r.fetch(R, *off)) return rc;
+        S.singletons += r.hc[C_SINGLETONS];
         S.total_list_entries += entries;
-        S.longest_list = std::max<u64>(S.longest_list, host_c[C_LONGEST]);
+        S.longest_list = std::max<u64>(S.longest_list, r.hc[C_LONGEST]);
     }
     S.records_written = b->kmers.size();
     if (merging) {   // these four describe the merged result
@@ -1672,17 +1673,8 @@ int lmat_db_build_from_genomes(lmat_ctx* ctx, lmat_build* b, uint64_t table_byte
     size_t mem_len = 0;
     FILE* w = open_memstream(&mem, &mem_len);
     if (!w) return lmat::set_err(ctx, LMAT_E_NOMEM, "open_memstream failed");
-    const uint32_t data_start = 29, version = 999, klen = (uint32_t)b->k;
-    const uint64_t count = b->kmers.size(), sanity = ~0ull;
-    const char loc = 'N';
-    fwrite(&data_start, 4, 1, w); fwrite(&count, 8, 1, w); fwrite(&sanity, 8, 1, w); fwrite(&version, 4, 1, w); fwrite(&loc, 1, 1, w); fwrite(&klen, 4, 1, w);
-    for (u64 i = 0; i < count; ++i) {
-        const u64 n = b->list_off[i + 1] - b->list_off[i];
-        const uint16_t n16 = (uint16_t)n;
-        fwrite(&b->kmers[i], 8, 1, w); fwrite(&n16, 2, 1, w); fwrite(&b->tids[b->list_off[i]], 4, n, w);
-        if ((i + 1) % 1500 == 0) fwrite(&sanity, 8, 1, w);
-    }
-    if (fclose(w) != 0 || !mem) { free(mem); return lmat::set_err(ctx, LMAT_E_NOMEM, "out of memory for the record stream"); }
+    const bool ok = write_records(w, b);
+    if (fclose(w) != 0 || !ok || !mem) { free(mem); return lmat::set_err(ctx, LMAT_E_NOMEM, "out of memory for the record stream"); }
     int rc = lmat_db_begin(ctx, b->k, 0, table_bytes);
     if (rc == LMAT_OK) {
         FILE* r = fmemopen(mem, mem_len, "rb");

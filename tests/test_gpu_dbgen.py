@@ -91,11 +91,9 @@ def test_goldens(eng, gold, tmp_path, fa, ref, k):
         e2.close()
 
 
-def test_chunk_and_pass_invariance(eng, gold, tmp_path):
+def _chunk_edge_records(tax):
     """One 10 kb and several 1 kb genomes; an N and a lower-case base within k - 1 of the edges of 4096-base chunks."""
-    k = 20
     rng = np.random.default_rng(7)
-    tax = dm.load_tree(gold["tree.dat"])
     leaves = sorted(t for t in tax.parent if tax.depth[t] == 6)
     big = bytearray(LETTERS[rng.integers(0, 4, 10000)].tobytes())
     for edge in (4096, 8192):   # the text starts with this record: its byte i is text position i
@@ -108,6 +106,13 @@ def test_chunk_and_pass_invariance(eng, gold, tmp_path):
         s[100:400] = big[2000 + 100 * j:2300 + 100 * j]   # shared with the big genome
         s[int(rng.integers(0, 1000))] = ord("N")
         recs.append((leaves[j * 5], bytes(s)))
+    return recs
+
+
+def test_chunk_and_pass_invariance(eng, gold, tmp_path):
+    k = 20
+    tax = dm.load_tree(gold["tree.dat"])
+    recs = _chunk_edge_records(tax)
     fa = _write_fasta(str(tmp_path / "g.fa"), recs, width=70)
     files = {}
     for chunk in (4096, 0):
@@ -120,6 +125,26 @@ def test_chunk_and_pass_invariance(eng, gold, tmp_path):
     for key, data in files.items():
         assert data == first, key
     _check_against_model(str(tmp_path / "o_4096_0.bin"), recs, tax, k, st)
+
+
+def test_pair_sort_equals_packed_sort(eng, gold, tmp_path, monkeypatch):
+    """LMAT_DBGEN_SORT=pairs (read per build): (owner, k-mer) pairs sorted twice write the bytes the one packed key writes."""
+    k = 20
+    tax = dm.load_tree(gold["tree.dat"])
+    recs = _chunk_edge_records(tax)
+    fa = _write_fasta(str(tmp_path / "g.fa"), recs, width=70)
+    packed = str(tmp_path / "packed.bin")
+    counts = lambda s: {n: v for n, v in s.items() if not n.endswith("_ms") and n not in ("passes", "prefix_bits")}
+    monkeypatch.delenv("LMAT_DBGEN_SORT", raising=False)
+    st = eng.build_taxhisto(fa, gold["tree.dat"], k, packed)
+    _check_against_model(packed, recs, tax, k, st)
+    monkeypatch.setenv("LMAT_DBGEN_SORT", "pairs")
+    for pb in (0, 2):
+        out = str(tmp_path / ("pairs_%d.bin" % pb))
+        st2 = eng.build_taxhisto(fa, gold["tree.dat"], k, out, prefix_bits=pb)
+        assert st2["passes"] == 1 << pb
+        assert open(out, "rb").read() == open(packed, "rb").read(), pb
+        assert counts(st2) == counts(st), pb
 
 
 def test_wide_fan_in(eng, tmp_path):

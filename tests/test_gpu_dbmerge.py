@@ -158,6 +158,21 @@ def test_pass_invariance(eng, gold, tmp_path):
     assert ei.value.code == E_CAPACITY
 
 
+def test_merge_only_one_pass_and_several(eng, gold, tmp_path):
+    """No FASTA: the count -> CSR tail of the merge alone, in one forced pass and in the several a small budget derives
+    (64 MiB of it are the fixed slack; 72 bytes a record and 12 an entry of about 18 000 records do not fit 768 KiB at once)."""
+    parts = [gold["a_p0_k20.bin"], gold["a_p1_k20.bin"]]
+    one = eng.merge_taxhisto(parts, gold["tree.dat"], 20, str(tmp_path / "one.bin"), prefix_bits=0)
+    many = eng.merge_taxhisto(parts, gold["tree.dat"], 20, str(tmp_path / "many.bin"), budget_bytes=(64 << 20) + (768 << 10))
+    assert one["passes"] == one["merge"]["passes"] == 1 and many["passes"] == many["merge"]["passes"] > 1
+    assert open(str(tmp_path / "one.bin"), "rb").read() == gold["whole"]
+    assert open(str(tmp_path / "many.bin"), "rb").read() == gold["whole"]
+    for n in ("singletons", "total_list_entries", "longest_list", "records_written"):
+        assert one[n] == many[n] == gold["whole_stats"][n], n
+    for n in ("records_one_source", "records_merged", "records_grown"):
+        assert one["merge"][n] == many["merge"][n], n
+
+
 def test_shapes_the_fixtures_lack(eng, tmp_path):
     """The 72-strain taxonomy of test_gpu_dbgen.test_wide_fan_in, its records dealt into three sources, with further records so
     that every situation listed at the end occurs; all of it against dm.model of all records together."""
