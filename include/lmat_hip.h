@@ -168,6 +168,10 @@ int lmat_debug_probe_stats(lmat_ctx* ctx, const uint64_t* kmers, uint64_t n, uin
  * read_label.cpp:821) against the IEEE division on every pair of its domain, and -- the two averages of the statistics, :806-880 --
  * on 2^26 drawn pairs (float >= 0, integer 1..64): out4 = {pairs that differ, pairs tried, drawn pairs that differ, drawn pairs tried}. */
 int lmat_debug_div_check(lmat_ctx* ctx, uint64_t* out4);
+/* Debug: which kernel the 160-k-mer fast class ran as -- its launches on a compact table with a 16-bit taxonomy and without -s (the
+ * instantiation the plain-run variant belongs to) on the context's device since the library was loaded, out2[0] by the generic
+ * kernel, out2[1] by the variant (LMAT_PLAIN=0 turns the variant off). */
+int lmat_debug_variant_launches(lmat_ctx* ctx, uint64_t* out2);
 
 /* Test hook for the synthetic database: what it must hold for the window of `species` (0-based) that starts at base `pos` of the
  * species ancestor -- the canonical k-mer and its taxid list (the strains that carry the window unmutated; with two or more

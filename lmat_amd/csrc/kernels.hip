@@ -1116,16 +1116,16 @@ __device__ __forceinline__ uint64_t bal(bool b) { return __builtin_amdgcn_ballot
 // The vector pipe is what the classify kernel runs out of, so this step is written for few VECTOR instructions: per-slot
 // loops read their operands as LDS broadcasts, four per load (a v_readlane is a vector instruction, a ds_read is not),
 // wave-uniform integers and lane masks stay on the scalar unit, and nothing branches per lane.
-template <int THM>
+template <int THM, bool PLAIN = false>   // PLAIN: see classify_one
 __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint32_t cand, const u32x4 fz, uint32_t my_cnt,
                                         uint32_t my_id, const unsigned int* hent, uint32_t* xch, GAS uint64_t* out,
                                         int valid_kmers, uint32_t len, int bin_sel) {
-    const float hbias = Ap->prm.hbias, sdiff = Ap->prm.sdiff;
+    const float hbias = PLAIN ? 0.0f : Ap->prm.hbias, sdiff = Ap->prm.sdiff;
     const int screen_phix = Ap->prm.screen_phix;
     // what does not depend on the read -- no null model, no debug stop outside 30 .. 34, depths that grow along every branch, candidates
     // only with -p (without it a multi match prints the lineage as built, :917-927: the general path's job; bin/run_rl.sh always
     // passes -p) -- is one bit the launcher worked out (k4_static_of)
-    if (!(Ap->prm.k4_static & 1)) return false;
+    if (!PLAIN && !(Ap->prm.k4_static & 1)) return false;
     const int stop = LMAT_ABLATE ? Ap->prm.stop_after : 0;   // 30..34: timing experiments (the step ends early with a placeholder record; ablation builds)
     auto placeholder = [&]() {
         if (lane == 0) {  // (on a zero the compiler cannot see through, as classify_one's emit: constant words would sit in registers across the read loop)
@@ -1414,7 +1414,7 @@ __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint
         res.call_score = call_score;
         call_idx = call_tid;
         // ---- candidates (:898-927): with -p all of them, best first; else, for a multi match, the lineage as built
-        if (Ap->cands) {
+        if (!PLAIN && Ap->cands) {
             GAS uint32_t* g_cursor = (GAS uint32_t*)Ap->cursor;
             const uint32_t reserve = nT;   // (-p: every candidate, best first)
             const uint32_t chunk = Ap->cand_chunk;
@@ -1835,7 +1835,12 @@ __global__ __launch_bounds__(256) void tail_kernel(ClassifyArgs A) {
 }
 
 typedef const ClassifyArgs __attribute__((address_space(4))) CArgs;
-template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false>
+// PLAIN (the 160-k-mer fast class only; launch_classify_t picks it per launch, plain_launch() is the list): the launch is the plain
+// run -- k = 20 in the compact layout (m = 17, two low bits), no null model, no -p candidates, no human bias, no rand / gene mode, no
+// debug stop, the decision on the wave and not by rows, every read of the batch taken in batch order, tails of four entries.  What
+// such a launch fixes is a literal here instead of a load through Ap, a compare and a branch per read, and the arms it cannot take
+// are not compiled.  No statement changes: PLAIN == false is the code as it was.
+template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false>
 __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned char* lds, LAS unsigned char* xl, int lane,
                                              const uint32_t* wcur, uint32_t (&nmacc)[2]) {
     using L = WL<U, T, E, INK4, CPT, WIDE>;
@@ -1904,7 +1909,8 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     uint16_t* el_plen = WIDE ? (uint16_t*)el_d + E : (uint16_t*)el_sp + E;   // path_len[ta]
     uint8_t* el_fl = (uint8_t*)(el_plen + E);    // flags[ta]
 
-    const int k = tb.k;
+    static_assert(!PLAIN || (U == 160 && CPT && !INK4 && !PERM && !WIDE && !LMAT_ABLATE), "PLAIN is a variant of the headline class");
+    const int k = PLAIN ? 20 : tb.k;
     const GAS uint64_t* g_slots = (const GAS uint64_t*)tb.slots;
     const GAS uint16_t* g_arena = (const GAS uint16_t*)tb.arena;
     const GAS uint32_t* g_tid32 = (const GAS uint32_t*)tb.tid32;
@@ -1948,7 +1954,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         return;
     }
     const uint32_t P = len - k + 1;
-    if (P < A.p_min || P > A.p_max) return;  // another launch over the same list takes this read
+    if (!PLAIN && (P < A.p_min || P > A.p_max)) return;  // another launch over the same list takes this read
     if (P > (uint32_t)U) {  // the host sizes U from the batch's longest read
         if (lane == 0) {
             emit(255, 0);
@@ -1962,8 +1968,8 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     constexpr bool TAILOK = CPT && U == 160 && !INK4;
     uint32_t tail_flag = 0;
     if constexpr (TAILOK) {
-        const uint32_t lpr = A.tail_lpr;
-        tail_flag = (uint32_t)__builtin_amdgcn_readfirstlane((lpr != 0 && P > 128u && P <= 128u + lpr && !A.nm.active) ? 1 : 0);  // (a scalar, not a lane mask re-materialised from its conditions)
+        const uint32_t lpr = PLAIN ? 4u : A.tail_lpr;
+        tail_flag = (uint32_t)__builtin_amdgcn_readfirstlane((lpr != 0 && P > 128u && P <= 128u + lpr && !(PLAIN ? 0u : A.nm.active)) ? 1 : 0);  // (a scalar, not a lane mask re-materialised from its conditions)
     }
     auto tail_mode = [&]() -> bool { return TAILOK && tail_flag != 0; };
     // ---- packed record -> LDS (coalesced), zero tail so windows past the end are invalid
@@ -2027,12 +2033,12 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     for (int c = 0; c < (CACHE ? CH : 1); ++c) {
         if (CACHE) { kreg[c] = 0; hreg[c] = 0; treg[c] = 0; okm[c] = 0; }
     }
-    const uint32_t want_gc = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.nm.active);  // (a scalar, not a lane mask)
+    const uint32_t want_gc = PLAIN ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)A.nm.active);  // (a scalar, not a lane mask)
     // compact layout: the minimizer of a k-mer is the smallest of the 4 m-mers it covers, and neighbouring k-mers
     // share 3 of them, so every lane scrambles ONE m-mer -- the one starting at its own position -- and the window
     // minimum runs over the lanes (cpt_finish).  u = scrambled canonical m-mer << 4 | (reverse strand is the smaller)
     // << 1 | (palindrome); bits 2..3 are left for the m-mer's place in the k-mer.
-    const int cm = tb.cpt.m;
+    const int cm = PLAIN ? 17 : tb.cpt.m;
     uint64_t ureg[KC];
     uint64_t fcm[KC];  // lanes whose forward strand is the canonical one
 #pragma unroll
@@ -2118,7 +2124,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         const uint32_t j = ((uint32_t)best >> 2) & 3u, fl = (uint32_t)best & 3u;
         const uint32_t strand = fc ? fl >> 1 : (fl == 0u ? 1u : 0u);  // the m-mer in the canonical k-mer is the larger of its pair
         const uint64_t sp = cpt_mix(best >> 4, cm);
-        const int lb = tb.cpt.lowbits;
+        const int lb = PLAIN ? 2 : tb.cpt.lowbits;
         const uint32_t hi = (uint32_t)(sp >> lb), low = (uint32_t)sp & ((1u << lb) - 1);
         // hi / W and hi mod W: a shift and a mask for the usual table sizes (W = 1, 2, 4, 8: 256 ... 32 GiB at k = 20), else the exact
         // double multiply of cpt_address (a 64-bit-float multiply and a 32-bit integer multiply are several issue slots each)
@@ -2142,7 +2148,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         for (int c = 0; c < CH; ++c) {
             if ((uint32_t)c * 64 >= len) break;
             if (TAILOK && c == 2 && tail_mode()) {  // looked up beforehand: k-mer, bucket, minimizer offset; the payload goes straight to its place
-                const uint32_t lpr = A.tail_lpr;
+                const uint32_t lpr = PLAIN ? 4u : A.tail_lpr;
                 const uint64_t ri = r - A.result_base;
                 u32x4 te = {0u, 0u, 0u, 0u};
                 uint64_t tu = 0;
@@ -2226,7 +2232,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     }
     WSYNC();
     nscan = nuniq;
-    if (A.prm.stop_after == 2) { if (lane == 0) { emit(250, nuniq); } return; }
+    if (!PLAIN && A.prm.stop_after == 2) { if (lane == 0) { emit(250, nuniq); } return; }
     RELANE();
     // ---- K2: probe in rounds.  FOUR lanes read one 64-byte bucket, 16 B (two slots) each: one wave-instruction
     //      covers 16 buckets, still one request per 64-byte line, and a 150 bp read's nine wave-loads are all in
@@ -2572,7 +2578,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     }
     if (nov) { ovf_pass(); WSYNC(); }
     nscan = P;
-    if (A.prm.stop_after == 2) { if (lane == 0) { emit(250, nuniq); } return; }
+    if (!PLAIN && A.prm.stop_after == 2) { if (lane == 0) { emit(250, nuniq); } return; }
     }
     STOP_AT(3, upay[0]);
     RELANE();
@@ -2693,13 +2699,13 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         }
         WSYNC();
     }
-    if (A.prm.stop_after == 4) { if (lane == 0) { emit(250, ndist); } return; }
+    if (!PLAIN && A.prm.stop_after == 4) { if (lane == 0) { emit(250, ndist); } return; }
     if (ndist == 0) {  // taxid_lst empty: NoDbHits record, proc_line :1270-1277
         if (lane == 0) { emit(LMAT_ST_NODBHITS, 0); nmacc[1]++; }
         return;
     }
     RELANE();
-    if (A.gene_mode) {
+    if (!PLAIN && A.gene_mode) {
         // ---- gene_label (src/gene_label.cpp:218-267, 288-313): the database maps a k-mer to a list of 32-bit gene ids;
         //      every distinct k-mer of the read votes for each gene of its list, genes are registered in first-seen order
         //      (k-mers in position order, then list order), and the call is the gene std::sort(Cmp: count descending) puts
@@ -2878,7 +2884,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         fnd += both >> 16;
         nel += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     }
-    if (A.prm.stop_after == 7) { if (lane == 0) { emit(250, nel > 65535u ? 65535u : nel); } return; }
+    if (!PLAIN && A.prm.stop_after == 7) { if (lane == 0) { emit(250, nel > 65535u ? 65535u : nel); } return; }
     bool overflow = nel > (uint32_t)E;
     if (overflow) {
         if (lane == 0) {
@@ -3307,7 +3313,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         return;
     }
     STOP_AT(6, nT);
-    if (A.rand_max) {  // rand_read_label: proc_line + construct_labels of src/rand_read_label.cpp:185-213,372-398
+    if (!PLAIN && A.rand_max) {  // rand_read_label: proc_line + construct_labels of src/rand_read_label.cpp:185-213,372-398
         const uint32_t gcb = ((const GAS uint8_t*)A.rand_gc)[r - A.result_base];
         GAS uint32_t* rmax = (GAS uint32_t*)A.rand_max;
         GAS uint32_t* rcnt = (GAS uint32_t*)A.rand_cnt;
@@ -3346,18 +3352,18 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         // Where the decision is made: tables of up to 16 taxids go to k4_row_kernel, four reads to a wave (status 251); larger ones
         // are decided right here on the wave (k4_wave) when the read qualifies; everything else -- null models, an effective human
         // bias, -y style experiments, more than 999 candidate k-mers ... -- takes the general path, by table size.
-        const bool rows = (A.prm.k4_static & 2) && nT <= 16u;
+        const bool rows = !PLAIN && (A.prm.k4_static & 2) && nT <= 16u;
         if constexpr (!INK4) {
             if (!rows) {
                 const uint32_t my_cnt = (uint32_t)lane < nT ? (uint32_t)cnt[lane] : 0u, my_id = (uint32_t)lane < nT ? (uint32_t)reg[lane] : 0u;
-                if (k4_wave<THM>(Ap, lane, nT, cand, fz, my_cnt, my_id, hent, (uint32_t*)(lds + L::OFF_R3), out, valid_kmers, len, bin_sel)) return;
+                if (k4_wave<THM, PLAIN>(Ap, lane, nT, cand, fz, my_cnt, my_id, hent, (uint32_t*)(lds + L::OFF_R3), out, valid_kmers, len, bin_sel)) return;
             }
         }
         GAS uint32_t* krec = (GAS uint32_t*)A.k4buf + (r - A.result_base) * kK4RecWords;
         if (lane < (int)nT) krec[2 + lane] = (uint32_t)reg[lane] | ((uint32_t)cnt[lane] << 16);
         if (lane == 0) {
             krec[0] = nT | (cand << 16);
-            emit(rows ? 251u : (A.nm.active ? 253u : (nT <= (uint32_t)kK4SmallT ? 254u : (nT <= (uint32_t)kK4MidT ? 252u : 253u))), cand);  // pending K4
+            emit(rows ? 251u : ((PLAIN ? 0u : A.nm.active) ? 253u : (nT <= (uint32_t)kK4SmallT ? 254u : (nT <= (uint32_t)kK4MidT ? 252u : 253u))), cand);  // pending K4
         }
         return;
     }
@@ -3878,7 +3884,7 @@ __global__ __launch_bounds__(64) void gather_bench_kernel(const uint64_t* __rest
 #define LMAT_FAST_WAVES 8   // (A/B builds: -DLMAT_FAST_WAVES=7 compiles the fast classes for 7 waves per SIMD, 72 registers)
 #endif
 constexpr int classify_waves(int U, int E, bool INK4, bool CPT) { return INK4 ? 1 : (E > kFastE ? (U <= 160 ? 5 : 2) : (U <= 160 ? (CPT ? LMAT_FAST_WAVES : 5) : (U <= 256 ? (CPT ? LMAT_FAST_WAVES : 5) : (U <= 320 ? (CPT ? 5 : 3) : (CPT ? 4 : 3))))); }
-template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false>
+template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false>
 __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_kernel(ClassifyArgs A) {
     extern __shared__ __align__(16) unsigned char lds_smem[];
     // U > 2048: the per-read tables of this workgroup live in global memory
@@ -3898,9 +3904,9 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
     uint32_t nmacc[2] = {0, 0};
     uint64_t off1 = 0;
     {
-        const uint64_t count = A.count_ptr ? (uint64_t)*(const GAS uint32_t*)A.count_ptr : A.count;
+        const uint64_t count = !PLAIN && A.count_ptr ? (uint64_t)*(const GAS uint32_t*)A.count_ptr : A.count;
         if (it >= count) return;
-        const GAS uint32_t* index = (const GAS uint32_t*)A.index;
+        const GAS uint32_t* index = PLAIN ? nullptr : (const GAS uint32_t*)A.index;
         const GAS uint64_t* rec_off = (const GAS uint64_t*)A.rec_off;
         const GAS uint32_t* words = (const GAS uint32_t*)A.words;
         auto r_of = [&](uint64_t i) -> uint64_t { return index ? (uint64_t)index[i] : A.first + i; };
@@ -3912,8 +3918,8 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
     while (true) {
         CArgs* Ap = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(Ap));  // (a fresh look at the arguments every trip: nothing derived from them is carried around the loop)
-        const uint64_t count = Ap->count_ptr ? (uint64_t)*(const GAS uint32_t*)Ap->count_ptr : Ap->count;  // (it < count here: checked before the first trip and by `more` after that)
-        const GAS uint32_t* index = (const GAS uint32_t*)Ap->index;
+        const uint64_t count = !PLAIN && Ap->count_ptr ? (uint64_t)*(const GAS uint32_t*)Ap->count_ptr : Ap->count;  // (it < count here: checked before the first trip and by `more` after that)
+        const GAS uint32_t* index = PLAIN ? nullptr : (const GAS uint32_t*)Ap->index;  // (PLAIN: the reads in batch order, their number in the arguments)
         const GAS uint64_t* rec_off = (const GAS uint64_t*)Ap->rec_off;
         const GAS uint32_t* words = (const GAS uint32_t*)Ap->words;
         auto r_of = [&](uint64_t i) -> uint64_t { return index ? (uint64_t)index[i] : Ap->first + i; };
@@ -3921,7 +3927,7 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
         const bool more = (uint64_t)it + G < count;
 #pragma unroll
         for (int j = 0; j < NW; ++j) wnext[j] = more ? words[off1 + lane + 64 * j] : 0u;
-        classify_one<U, T, E, INK4, PERM, CPT, WIDE>(Ap, r_of(it), smem, xl, lane, wcur, nmacc);
+        classify_one<U, T, E, INK4, PERM, CPT, WIDE, PLAIN>(Ap, r_of(it), smem, xl, lane, wcur, nmacc);
         WSYNC();
 #pragma unroll
         for (int j = 0; j < NW; ++j) wcur[j] = wnext[j];
@@ -4104,11 +4110,38 @@ static int k4_static_of(const ClassifyArgs& a) {
     const bool rows = base && a.prm.k4_row && stop == 0;
     return (wave ? 1 : 0) | (rows ? 2 : 0);
 }
-template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false>
+// The plain run (classify_one's PLAIN): every launch-wide value the variant has as a literal, checked here.  What stays a run-time
+// scalar in it -- the bucket width in its three forms, sdiff, the k-mer and score thresholds, the PhiX screen -- is not asked
+// about.  LMAT_PLAIN=0 sends every launch to the generic kernel (A/B runs; ablation builds have no variant).
+static bool plain_launch(const ClassifyArgs& a, int k4_static) {
+    static const bool on = !LMAT_ABLATE && (!getenv("LMAT_PLAIN") || atoi(getenv("LMAT_PLAIN")) != 0);
+    return on && a.tb.k == 20 && a.tb.cpt.nb && a.tb.cpt.m == 17 && a.tb.cpt.lowbits == 2 && !a.tb.wide && !a.nm.active && !a.rand_max &&
+           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 1 && !a.cands && a.prm.hbias == 0.0f &&
+           a.p_min == 0 && a.p_max == 0xFFFFFFFFu && !a.index && !a.count_ptr && a.tail_lpr == 4;
+}
+// launches of <160, 64, kFastE> on a compact 16-bit table without -s (the class PLAIN is a variant of) by kernel, per device: [0] the
+// generic instantiation, [1] PLAIN (lmat_debug_variant_launches)
+static std::atomic<unsigned long long> g_variant_launches[64][2];
+void classify_variant_launches(int device, uint64_t out[2]) {
+    out[0] = out[1] = 0;
+    if (device < 0 || device >= 64) return;
+    out[0] = g_variant_launches[device][0].load();
+    out[1] = g_variant_launches[device][1].load();
+}
+template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false>
 static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     using L = WL<U, T, E, INK4, CPT, WIDE>;
     ClassifyArgs a = a_in;
     a.prm.k4_static = k4_static_of(a);
+    // the instantiation the variant belongs to: only its launches are asked about, and only they are counted
+    constexpr bool kPlainClass = U == 160 && T == 64 && E == kFastE && !INK4 && !PERM && CPT && !WIDE;
+    if constexpr (kPlainClass && !PLAIN && !LMAT_ABLATE) {
+        if (plain_launch(a, a.prm.k4_static)) { launch_classify_t<U, T, E, INK4, PERM, CPT, WIDE, true>(a_in, stream); return; }
+    }
+    if constexpr (kPlainClass) {
+        int dev = 0;   // (the current device, asked for as PerDeviceOnce does)
+        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) g_variant_launches[dev][PLAIN ? 1 : 0]++;
+    }
     if (U > 2048) {  // tables in global memory: few workgroups; LDS only for the compact probe's scratch block
         int grid = kGmemGrid;
         if (!a.count_ptr && (uint64_t)grid > a.count) grid = (int)(a.count ? a.count : 1);
@@ -4118,7 +4151,7 @@ static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     static const int lds_pad = getenv("LMAT_LDS_PAD") ? atoi(getenv("LMAT_LDS_PAD")) : 0;  // experiments: fewer resident waves
     const int lds_bytes = L::BYTES + lds_pad;
     static PerDeviceOnce attr_once;
-    attr_once([lds_bytes] { hipFuncSetAttribute((const void*)classify_kernel<U, T, E, INK4, PERM, CPT, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
+    attr_once([lds_bytes] { hipFuncSetAttribute((const void*)classify_kernel<U, T, E, INK4, PERM, CPT, WIDE, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
     // one single-wave workgroup per read slot; enough groups to fill every CU's LDS several times over
     const int per_cu = 160 * 1024 / lds_bytes;
     // Reads differ in cost (one over genus-shared k-mers takes 3-4 times the usual), and a block keeps its share of the batch:
@@ -4129,7 +4162,7 @@ static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     if (!a.count_ptr && (uint64_t)grid > a.count) grid = (int)a.count;
     if (a.count_ptr && INK4 && grid > 256 * (per_cu < 2 ? 2 : per_cu)) grid = 256 * (per_cu < 2 ? 2 : per_cu);  // the lists of the large classes are short (the E = 512 class may get a tenth of a batch): a block per wave the LDS holds
     if (grid < 1) grid = 1;
-    classify_kernel<U, T, E, INK4, PERM, CPT, WIDE><<<dim3(grid), dim3(64), lds_bytes, stream>>>(a);
+    classify_kernel<U, T, E, INK4, PERM, CPT, WIDE, PLAIN><<<dim3(grid), dim3(64), lds_bytes, stream>>>(a);
 }
 
 void launch_k4_debug(const ClassifyArgs& a, const uint32_t* idx, const float* scores, const uint64_t* off, const float* stdevs, uint64_t n,

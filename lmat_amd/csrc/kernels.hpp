@@ -92,6 +92,8 @@ void launch_k4_debug(const ClassifyArgs& a, const uint32_t* idx, const float* sc
                      hipStream_t stream);
 void launch_k4_debug_counts(const ClassifyArgs& a, const uint32_t* idx, const uint32_t* cnts, const uint64_t* off, const uint32_t* cands, uint64_t n,
                             bool on_the_wave, hipStream_t stream);
+// launches of the 160-k-mer fast class (compact table, 16-bit ids, no -s) on `device` so far, by kernel: out[0] the generic instantiation, out[1] the PLAIN variant
+void classify_variant_launches(int device, uint64_t out[2]);
 int classify_max_read_len();
 size_t classify_gmem_scratch_bytes();
 // issues ~n_probes random bucket reads (rounded up to 144 per wave x 4096 waves)

@@ -2040,6 +2040,14 @@ int lmat_debug_last_counters(lmat_ctx* c, uint32_t* out16) {
     return LMAT_OK;
 }
 
+// Which kernel the 160-k-mer fast class ran as: launches on this context's device since the library was loaded, out2[0] by the generic
+// instantiation, out2[1] by the plain-run variant (kernels.hip plain_launch; LMAT_PLAIN=0 turns the variant off).
+int lmat_debug_variant_launches(lmat_ctx* c, uint64_t* out2) {
+    if (!c || !out2) return LMAT_E_ARG;
+    classify_variant_launches(c->device, out2);
+    return LMAT_OK;
+}
+
 int lmat_last_timing(const lmat_ctx* c, float* classify_ms, float* decide_ms, uint64_t* launches) {
     if (!c) return LMAT_E_ARG;
     if (classify_ms) *classify_ms = c->last_classify_ms;

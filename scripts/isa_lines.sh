@@ -1,8 +1,10 @@
 #!/bin/bash
 # scripts/isa_lines.sh FROM TO [kernel-substring]: the headline kernel's instructions whose debug line lies in kernels.hip:[FROM, TO]
+# (default: the PLAIN variant <160,64,256,false,false,true,false,true>, which the plain run launches; its generic instantiation is
+# classify_kernelILi160ELi64ELi256ELb0ELb0ELb1ELb0ELb0E)
 # (compiled with -gline-tables-only into /tmp/isa; pass REBUILD=1 after editing kernels.hip)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-K=${3:-classify_kernelILi160ELi64ELi256ELb0ELb0ELb1ELb0}
+K=${3:-classify_kernelILi160ELi64ELi256ELb0ELb0ELb1ELb0ELb1E}
 mkdir -p /tmp/isa
 if [ -n "$REBUILD" ] || [ ! -f /tmp/isa/kg.s ] || [ $ROOT/lmat_amd/csrc/kernels.hip -nt /tmp/isa/kg.s ]; then
   /opt/rocm/bin/hipcc -std=c++17 -O3 -fPIC -ffp-contract=off --offload-arch=gfx950 -gline-tables-only -S --cuda-device-only -o /tmp/isa/kg.s $ROOT/lmat_amd/csrc/kernels.hip 2>/dev/null
