@@ -433,6 +433,43 @@ int lmat_build_merge_stats(const lmat_build* b, lmat_merge_stats* out);   /* aft
  * on the device.  *n is the number of such taxids, set even when cap is too small (LMAT_E_CAPACITY): a cap of 0 asks for it. */
 int lmat_build_taxid_counts(lmat_build* b, uint32_t* tids, uint64_t* counts, uint64_t cap, uint64_t* n);
 
+/* ---- per-group k-mer coverage of a set of reads (content_summ's counting, src/content_summ.cpp:113-152, 538-571) ----
+ * Input: reads (ASCII, any length, 0 included) with a caller-chosen 32-bit group id each -- content_summ uses the taxid it counts
+ * the read under -- and a list of k sizes in 1..31 (duplicates allowed, reported per index).
+ * Per read and k: every window of k consecutive ACGTacgt bytes gives min(forward, reverse complement) over A=0 C=1 G=2 T=3; any
+ * other byte and a read boundary break the run; the SET of distinct canonical k-mers of the read is what counts.
+ * Per group and k: the multiplicity of a k-mer is the number of reads of the group whose set holds it; reported are `distinct`
+ * (number of k-mers), `total` (sum of multiplicities) and the histogram multiplicity -> number of k-mers.  Groups without a
+ * k-mer for a k are absent from that k's report.  The result is a function of the multiset of (group, read): not of the order
+ * or batching of lmat_cov_add_reads, the budget or the pass split.
+ *   lmat_cov_set_options   device_budget_bytes 0: half of the free device memory; prefix_bits -1: derived per k, else every k's
+ *                          k-mer space is cut into 2^min(prefix_bits, 2k) passes by the top bits of the canonical k-mer
+ *   lmat_cov_add_reads     read i = ascii[off[i] .. off[i+1]); a failed call adds nothing
+ *   lmat_cov_run           once per object; without reads LMAT_OK and empty reports
+ *   lmat_cov_summary       ascending by group id;  lmat_cov_histogram  ascending by multiplicity.  Both set *n even when cap is
+ *                          too small (LMAT_E_CAPACITY): a cap of 0 asks for the size.  A group the summary does not list gives
+ *                          *n = 0 and LMAT_OK from lmat_cov_histogram.
+ *   errors   a k outside 1..31, n_k < 1, a NULL array with n_reads > 0, an off that does not ascend, a fetch before the run, a
+ *            second run: LMAT_E_ARG.  More than 2^32 - 1 reads: LMAT_E_CAPACITY.  A pass that does not fit the budget under a
+ *            forced prefix_bits, or under the finest derived split: LMAT_E_CAPACITY; nothing is ever cut short. */
+typedef struct lmat_cov lmat_cov;
+typedef struct {
+    uint64_t reads, bases;
+    uint64_t windows;        /* valid windows, summed over k */
+    uint64_t runs;           /* distinct (group, k-mer), summed over k */
+    uint32_t passes;         /* summed over k */
+    uint32_t prefix_bits;    /* the finest split any k ran under */
+    float extract_ms, sort_ms, segment_ms, histogram_ms;
+} lmat_cov_stats;
+int lmat_cov_create(lmat_ctx* ctx, const int* k_sizes, int n_k, lmat_cov** out);      /* no taxonomy or database needed */
+void lmat_cov_destroy(lmat_cov* c);
+const char* lmat_cov_error(const lmat_cov* c);
+int lmat_cov_set_options(lmat_cov* c, uint64_t device_budget_bytes /* 0: half of free */, int prefix_bits /* -1: derive */);
+int lmat_cov_add_reads(lmat_cov* c, const uint8_t* ascii, const uint64_t* off /* n+1 */, uint64_t n_reads, const uint32_t* group);
+int lmat_cov_run(lmat_cov* c, lmat_cov_stats* out);
+int lmat_cov_summary(lmat_cov* c, int k_index, uint32_t* groups, uint64_t* distinct, uint64_t* total, uint64_t cap, uint64_t* n);
+int lmat_cov_histogram(lmat_cov* c, int k_index, uint32_t group, uint64_t* multiplicity, uint64_t* n_kmers, uint64_t cap, uint64_t* n);
+
 /* ---- test hook: the decision step on given candidate tables ---------------------------------
  * Runs the decision kernels' own code -- std::sort(TCmp) (src/read_label.cpp:475-485, 892-893) and findReadLabelVer2
  * (:284-419) -- on n candidate tables given from outside instead of computed from reads: table i = the (32-bit taxid,

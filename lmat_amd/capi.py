@@ -48,6 +48,16 @@ class MergeStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CovStats(C.Structure):
+    """lmat_cov_stats: what lmat_cov_run counted and the HIP-event time of every stage."""
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("windows", C.c_uint64), ("runs", C.c_uint64), ("passes", C.c_uint32),
+                ("prefix_bits", C.c_uint32), ("extract_ms", C.c_float), ("sort_ms", C.c_float), ("segment_ms", C.c_float),
+                ("histogram_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 READ_RESULT_DTYPE = np.dtype([("status", "u1"), ("match_type", "u1"), ("cand_kmer_cnt", "<u2"), ("valid_kmers", "<i4"),
                               ("read_len", "<i4"), ("log_avg", "<f4"), ("stdev", "<f4"), ("call_tid", "<u4"),
                               ("call_score", "<f4"), ("cand_off", "<u4"), ("n_cand", "<u4"), ("bin_sel", "<i4")])
@@ -168,6 +178,14 @@ def load_library(path: str | None = None):
         "lmat_build_add_taxhisto": (i32, [vp, cp]),
         "lmat_build_merge_stats": (i32, [vp, P(MergeStats)]),
         "lmat_build_taxid_counts": (i32, [vp, vp, vp, u64, P(u64)]),
+        "lmat_cov_create": (i32, [vp, vp, i32, P(vp)]),
+        "lmat_cov_destroy": (None, [vp]),
+        "lmat_cov_error": (cp, [vp]),
+        "lmat_cov_set_options": (i32, [vp, u64, i32]),
+        "lmat_cov_add_reads": (i32, [vp, vp, vp, u64, vp]),
+        "lmat_cov_run": (i32, [vp, P(CovStats)]),
+        "lmat_cov_summary": (i32, [vp, i32, vp, vp, vp, u64, P(u64)]),
+        "lmat_cov_histogram": (i32, [vp, i32, u32, vp, vp, u64, P(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -193,7 +211,9 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check", "lmat_debug_variant_launches",
             "lmat_build_create", "lmat_build_destroy", "lmat_build_error", "lmat_build_set_options", "lmat_build_add_fasta", "lmat_build_add_sequence",
             "lmat_build_run", "lmat_build_write_taxhisto", "lmat_build_fetch", "lmat_db_build_from_genomes",
-            "lmat_build_add_taxhisto", "lmat_build_merge_stats", "lmat_build_taxid_counts"]
+            "lmat_build_add_taxhisto", "lmat_build_merge_stats", "lmat_build_taxid_counts",
+            "lmat_cov_create", "lmat_cov_destroy", "lmat_cov_error", "lmat_cov_set_options", "lmat_cov_add_reads", "lmat_cov_run",
+            "lmat_cov_summary", "lmat_cov_histogram"]
 
 
 def _ptr(a):
@@ -421,6 +441,83 @@ class Builder:
             self.h = None
 
 
+class Coverage:
+    """lmat_cov: reads with a group id each -> per group and k the distinct canonical k-mers, the sum of their multiplicities
+    (reads of the group that hold the k-mer) and the histogram of the multiplicities, on the GPU of `eng`."""
+
+    def __init__(self, eng, k_sizes):
+        self.eng, self.lib = eng, eng.lib
+        self.k_sizes = [int(k) for k in k_sizes]
+        ks = np.asarray(self.k_sizes, dtype=np.int32)
+        h = C.c_void_p()
+        eng._chk(self.lib.lmat_cov_create(eng.ctx, _ptr(ks) if ks.size else None, int(ks.size), C.byref(h)))
+        self.h = h
+        self.stats = None
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise LmatError(rc, self.lib.lmat_cov_error(self.h).decode(errors="replace"))
+
+    def set_options(self, budget_bytes=0, prefix_bits=-1):
+        self._chk(self.lib.lmat_cov_set_options(self.h, int(budget_bytes), int(prefix_bits)))
+
+    def add_reads(self, reads, groups):
+        """reads: byte strings (or str); groups: one 32-bit id per read."""
+        bs = [r.encode() if isinstance(r, str) else bytes(r) for r in reads]
+        off = np.zeros(len(bs) + 1, dtype=np.uint64)
+        if bs:
+            np.cumsum([len(b) for b in bs], out=off[1:])
+        blob = np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8)
+        g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32))
+        if g.size != len(bs):
+            raise ValueError("one group id per read")
+        self._chk(self.lib.lmat_cov_add_reads(self.h, _ptr(blob), _ptr(off), len(bs), _ptr(g)))
+
+    def run(self):
+        st = CovStats()
+        self._chk(self.lib.lmat_cov_run(self.h, C.byref(st)))
+        self.stats = st.as_dict()
+        return self.stats
+
+    def summary(self, k_index):
+        """-> (groups uint32[n] ascending, distinct uint64[n], total uint64[n])"""
+        n = C.c_uint64(0)
+        rc = self.lib.lmat_cov_summary(self.h, k_index, None, None, None, 0, C.byref(n))
+        if rc != 0 and n.value == 0:
+            self._chk(rc)
+        g = np.zeros(max(n.value, 1), dtype=np.uint32)
+        d = np.zeros(max(n.value, 1), dtype=np.uint64)
+        t = np.zeros(max(n.value, 1), dtype=np.uint64)
+        self._chk(self.lib.lmat_cov_summary(self.h, k_index, _ptr(g), _ptr(d), _ptr(t), n.value, C.byref(n)))
+        return g[:n.value], d[:n.value], t[:n.value]
+
+    def histogram(self, k_index, group):
+        """-> [(multiplicity, n_kmers), ...] ascending; [] for a group the summary does not list"""
+        n = C.c_uint64(0)
+        rc = self.lib.lmat_cov_histogram(self.h, k_index, int(group), None, None, 0, C.byref(n))
+        if rc != 0 and n.value == 0:
+            self._chk(rc)
+        if n.value == 0:
+            return []
+        m = np.zeros(n.value, dtype=np.uint64)
+        c = np.zeros(n.value, dtype=np.uint64)
+        self._chk(self.lib.lmat_cov_histogram(self.h, k_index, int(group), _ptr(m), _ptr(c), n.value, C.byref(n)))
+        return [(int(a), int(b)) for a, b in zip(m[:n.value], c[:n.value])]
+
+    def report(self):
+        """-> {k_index: {group: (distinct, total, [(multiplicity, n_kmers), ...])}}"""
+        out = {}
+        for ki in range(len(self.k_sizes)):
+            g, d, t = self.summary(ki)
+            out[ki] = {int(a): (int(b), int(c), self.histogram(ki, int(a))) for a, b, c in zip(g, d, t)}
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.lmat_cov_destroy(self.h)
+            self.h = None
+
+
 class Engine:
     """One context on one GPU (lmat_ctx)."""
 
@@ -517,6 +614,18 @@ class Engine:
             return b.stats
         finally:
             b.close()
+
+    # per-group k-mer coverage (lmat_cov_*) --------------------------------------------
+    def kmer_coverage(self, reads, groups, k_sizes, budget_bytes=0, prefix_bits=-1):
+        """content_summ's counting: -> ({k_index: {group: (distinct, total, [(multiplicity, n_kmers), ...])}}, statistics)."""
+        c = Coverage(self, k_sizes)
+        try:
+            c.set_options(budget_bytes, prefix_bits)
+            c.add_reads(reads, groups)
+            st = c.run()
+            return c.report(), st
+        finally:
+            c.close()
 
     def load_image(self, path, table_bytes=0):
         self._chk(self.lib.lmat_db_load_image(self.ctx, path.encode(), table_bytes))

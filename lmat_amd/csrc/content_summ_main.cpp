@@ -12,7 +12,15 @@
 //   * a called taxid without a rank-table entry reads as rank "" (operator[] inserts): a file "<o>._kmer_cov" appears;
 //   * strain -> species folding uses the FIRST species on the path (map::insert keeps the first, :342-351);
 //   * a read's k-mers are counted once per read (set no_dups, :131-150).
+//
+// -G (a letter upstream's getopt string leaves free) or LMAT_CS_GPU=1 moves the k-mer counting to the GPU: the engine is loaded at
+// run time (LMAT_LIB, else ../liblmat_hip.so beside the executable), the workers keep the text and the taxid of every selected read
+// instead of counting, one lmat_cov_run (include/lmat_hip.h) serves all k sizes, and the rows are printed from its
+// reports by the same statements.  Without the switch nothing of this is touched and no library is loaded.  There is no fallback:
+// a library that cannot be loaded, no usable HIP device or a failing lmat_cov_* call ends the run with a message and a non-zero exit.
+#include <dlfcn.h>
 #include <getopt.h>
+#include <unistd.h>
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -28,6 +36,7 @@
 #include <unordered_set>
 #include <vector>
 #include "outfmt.hpp"
+#include "../../include/lmat_hip.h"   // types and prototypes only: the functions are looked up with dlsym
 
 #define LMAT_VERSION "1.2.4_2018a"
 
@@ -138,13 +147,125 @@ static void comp_kmer_cov(const std::vector<std::vector<std::map<tid_t, kmer_cnt
     }
 }
 
+// The engine, loaded at run time, and the coverage object of the run (-G / LMAT_CS_GPU=1).
+struct GpuCov {
+    void* so = nullptr;
+    decltype(&lmat_ctx_create) ctx_create = nullptr;
+    decltype(&lmat_ctx_destroy) ctx_destroy = nullptr;
+    decltype(&lmat_cov_create) create = nullptr;
+    decltype(&lmat_cov_destroy) destroy = nullptr;
+    decltype(&lmat_cov_error) error = nullptr;
+    decltype(&lmat_cov_add_reads) add_reads = nullptr;
+    decltype(&lmat_cov_run) run = nullptr;
+    decltype(&lmat_cov_summary) summary = nullptr;
+    decltype(&lmat_cov_histogram) histogram = nullptr;
+    lmat_ctx* ctx = nullptr;
+    lmat_cov* cov = nullptr;
+    lmat_cov_stats stats;
+    std::vector<std::map<tid_t, std::pair<uint64_t, uint64_t>>> summ;   // [k index][taxid] -> (distinct, total)
+
+    [[noreturn]] void fail(const std::string& what, int rc) {
+        std::cerr << "content_summ -G: " << what << " failed (" << rc << "): " << (cov ? error(cov) : "") << std::endl;
+        exit(1);
+    }
+    template <class F> void sym(F& f, const char* name, const std::string& lib) {
+        f = reinterpret_cast<F>(dlsym(so, name));
+        if (!f) { std::cerr << "content_summ -G: " << lib << " has no " << name << ": " << dlerror() << std::endl; exit(1); }
+    }
+    void open(const std::vector<int>& k_size) {
+        std::string lib;
+        if (const char* e = getenv("LMAT_LIB")) lib = e;
+        if (lib.empty()) {
+            char self[4096];
+            const ssize_t n = readlink("/proc/self/exe", self, sizeof(self) - 1);
+            std::string dir = n > 0 ? std::string(self, (size_t)n) : std::string(".");
+            const size_t sl = dir.rfind('/');
+            dir = sl == std::string::npos ? "." : dir.substr(0, sl);
+            lib = dir + "/../liblmat_hip.so";
+        }
+        so = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!so) { std::cerr << "content_summ -G: cannot load " << lib << ": " << dlerror() << std::endl; exit(1); }
+        sym(ctx_create, "lmat_ctx_create", lib);
+        sym(ctx_destroy, "lmat_ctx_destroy", lib);
+        sym(create, "lmat_cov_create", lib);
+        sym(destroy, "lmat_cov_destroy", lib);
+        sym(error, "lmat_cov_error", lib);
+        sym(add_reads, "lmat_cov_add_reads", lib);
+        sym(run, "lmat_cov_run", lib);
+        sym(summary, "lmat_cov_summary", lib);
+        sym(histogram, "lmat_cov_histogram", lib);
+        int rc = ctx_create(0, nullptr, &ctx);
+        if (rc != LMAT_OK) {   // no context, so no message of the library's: LMAT_E_DEVICE is what it returns without a device it can set up
+            if (rc == LMAT_E_DEVICE) std::cerr << "content_summ -G: no usable HIP device (lmat_ctx_create: LMAT_E_DEVICE)";
+            else std::cerr << "content_summ -G: lmat_ctx_create failed with code " << rc << (rc == LMAT_E_NOMEM ? " (out of memory)" : "");
+            std::cerr << "; there is no host fallback with -G" << std::endl;
+            exit(1);
+        }
+        rc = create(ctx, k_size.data(), (int)k_size.size(), &cov);
+        if (rc != LMAT_OK) { std::cerr << "content_summ -G: lmat_cov_create failed (" << rc << ")" << std::endl; exit(1); }
+    }
+    // the selected reads of one file, in file order
+    void add(const std::vector<std::string>& reads, const std::vector<tid_t>& tids) {
+        std::string blob;
+        std::vector<uint64_t> off(1, 0);
+        for (const std::string& r : reads) { blob += r; off.push_back(blob.size()); }
+        blob.push_back('\0');
+        const int rc = add_reads(cov, (const uint8_t*)blob.data(), off.data(), reads.size(), tids.data());
+        if (rc != LMAT_OK) fail("lmat_cov_add_reads", rc);
+    }
+    void count(size_t n_k) {
+        int rc = run(cov, &stats);
+        if (rc != LMAT_OK) fail("lmat_cov_run", rc);
+        summ.resize(n_k);
+        for (size_t ksi = 0; ksi < n_k; ++ksi) {
+            uint64_t n = 0;
+            rc = summary(cov, (int)ksi, nullptr, nullptr, nullptr, 0, &n);
+            if (rc != LMAT_OK && rc != LMAT_E_CAPACITY) fail("lmat_cov_summary", rc);
+            std::vector<uint32_t> g(n + 1);
+            std::vector<uint64_t> d(n + 1), t(n + 1);
+            rc = summary(cov, (int)ksi, g.data(), d.data(), t.data(), n, &n);
+            if (rc != LMAT_OK) fail("lmat_cov_summary", rc);
+            for (uint64_t i = 0; i < n; ++i) summ[ksi][g[i]] = std::make_pair(d[i], t[i]);
+        }
+    }
+    void close() {
+        if (cov) destroy(cov);
+        if (ctx) ctx_destroy(ctx);
+        cov = nullptr;
+        ctx = nullptr;
+    }
+};
+
+// comp_kmer_cov from the device's reports: the same lines through the same types
+static void comp_kmer_cov_gpu(GpuCov& G, tid_t tid, std::ofstream& ofs, const std::vector<int>& kv) {
+    for (unsigned ksi = 0; ksi < kv.size(); ++ksi) {
+        uint64_t kmer_cnt = 0;
+        int kcnt_sum = 0;
+        auto it = G.summ[ksi].find(tid);
+        if (it != G.summ[ksi].end()) { kmer_cnt = it->second.first; kcnt_sum = (int)(uint32_t)it->second.second; }
+        uint64_t n = 0;
+        int rc = G.histogram(G.cov, (int)ksi, tid, nullptr, nullptr, 0, &n);
+        if (rc != LMAT_OK && rc != LMAT_E_CAPACITY) G.fail("lmat_cov_histogram", rc);
+        std::vector<uint64_t> mult(n + 1), cnt(n + 1);
+        if (n) {
+            rc = G.histogram(G.cov, (int)ksi, tid, mult.data(), cnt.data(), n, &n);
+            if (rc != LMAT_OK) G.fail("lmat_cov_histogram", rc);
+        }
+        ofs << "taxid=" << tid << " distinct_kmer_cnt=" << kmer_cnt << " k_size=" << kv[ksi] << " tot_kmer_cnt=" << kcnt_sum << std::endl;
+        for (uint64_t i = 0; i < n; ++i) ofs << tid << " " << kv[ksi] << " " << (unsigned)(int)mult[i] << " " << (unsigned)cnt[i] << std::endl;
+    }
+}
+
 int main(int argc, char* argv[]) {
     float threshold = 0.0f;
     std::string query_fn_lst, lmat_sum, ofbase, tax_tree_fn, rank_table_file, low_num_plasmid_file, k_size_str, rank_check_str;
     bool skip_human = false, do_human_reg = false;
+    bool gpu = false;
+    if (const char* e = getenv("LMAT_CS_GPU")) gpu = !strcmp(e, "1");
     int c;
-    while ((c = getopt(argc, argv, "m:f:a:h:njb:ye:wp:k:c:v:k:i:d:l:t:sr:o:x:f:q:V")) != -1) {
+    while ((c = getopt(argc, argv, "m:f:a:h:njb:ye:wp:k:c:v:k:i:d:l:t:sr:o:x:f:q:VG")) != -1) {
         switch (c) {
+            case 'G': gpu = true; break;
             case 'n': do_human_reg = true; break;
             case 'a': rank_check_str = optarg; break;
             case 'p': low_num_plasmid_file = optarg; break;
@@ -177,6 +298,8 @@ int main(int argc, char* argv[]) {
         while (std::getline(ss, tok, ',')) if (!tok.empty()) { std::cout << "rank store: [" << tok << "]" << std::endl; rank_check.insert(tok); }
     }
     for (int k : k_size) std::cout << "track k size=" << k << std::endl;
+    GpuCov G;
+    if (gpu) G.open(k_size);   // before any work: without the engine or a device the run ends here
     if (!low_num_plasmid_file.empty()) {
         std::ifstream ifs(low_num_plasmid_file.c_str());
         if (!ifs) std::cerr << "Unexpected reading error: " << low_num_plasmid_file << std::endl;
@@ -236,6 +359,8 @@ int main(int argc, char* argv[]) {
     }
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<std::vector<std::map<tid_t, kmer_cnt_t>>> kmer_track(n_threads, std::vector<std::map<tid_t, kmer_cnt_t>>(k_size.size()));
+    std::vector<std::vector<std::string>> sel_read(n_threads);   // -G: the selected reads of every file and the taxid each counts under
+    std::vector<std::vector<tid_t>> sel_tid(n_threads);
     {
         std::vector<std::thread> th;
         std::vector<int> bad(n_threads, 0);
@@ -263,12 +388,22 @@ int main(int argc, char* argv[]) {
                     if (s2 != strain2spec.end() && !is_plasmid(taxid)) use_tid = s2->second;
                     auto rk = rank_table.find(use_tid);
                     const std::string rnk = rk != rank_table.end() ? rk->second : "undef";
-                    if (rank_check.count(rnk) || is_plasmid(taxid)) store_kmers(read_buff, k_size, use_tid, kmer_track[t]);
+                    if (rank_check.count(rnk) || is_plasmid(taxid)) {
+                        if (gpu) { sel_read[t].push_back(read_buff); sel_tid[t].push_back(use_tid); }
+                        else store_kmers(read_buff, k_size, use_tid, kmer_track[t]);
+                    }
                 }
             });
         for (auto& x : th) x.join();
         for (int t = 0; t < n_threads; ++t)
             if (bad[t]) { std::cerr << "did not open for reading: [" << files[t] << "] tid: [" << t << "]" << std::endl; return -1; }
+    }
+    if (gpu) {
+        for (int t = 0; t < n_threads; ++t) {
+            G.add(sel_read[t], sel_tid[t]);
+            std::vector<std::string>().swap(sel_read[t]);
+        }
+        G.count(k_size.size());
     }
     // the tree of the called taxids (:415-440) and its walk, children in reverse order of arrival (:447-536)
     std::set<tid_t> seen;
@@ -313,7 +448,10 @@ int main(int argc, char* argv[]) {
                     if (!(*made)) std::cout << "Unable to write to " << fn << " will try to continue" << std::endl;
                     rank_ofs.insert(std::make_pair(rank, made));  // upstream's `kos` stays NULL here: the first node of a rank writes no rows
                 }
-                if (kos && tot_read_cnt > 1) comp_kmer_cov(kmer_track, tid, *kos, k_size);
+                if (kos && tot_read_cnt > 1) {
+                    if (gpu) comp_kmer_cov_gpu(G, tid, *kos, k_size);
+                    else comp_kmer_cov(kmer_track, tid, *kos, k_size);
+                }
             }
         }
         std::string s = tab_lst[tid];
@@ -324,6 +462,10 @@ int main(int argc, char* argv[]) {
         ofs << s << std::endl;
     }
     for (auto& p : rank_ofs) { p.second->close(); delete p.second; }
+    if (gpu) {
+        std::cout << "kmer coverage on device: reads=" << G.stats.reads << " windows=" << G.stats.windows << " passes=" << G.stats.passes << std::endl;
+        G.close();
+    }
     std::cout << "query time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << std::endl;
     return 0;
 }

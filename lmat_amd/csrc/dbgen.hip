@@ -24,7 +24,8 @@
 // hist_kernel counts, for either kind of run, the result records whose list holds each taxid (countTaxidFrequency's map).
 //
 // Written once for both: the walk (closure_walk, over a sequence accessor: OwnerSeq for the build, TourSeq for the merge) with claim_long,
-// count_list and rank_store around it on the device; on the host the count -> CSR tail (write_lists), with_temp, LapTimer and write_records.
+// count_list and rank_store around it on the device; on the host the count -> CSR tail (write_lists) and write_records.  The text scan of the
+// extraction, the wave helpers, DevBuf, with_temp and LapTimer are kmer_dev.hpp's, shared with kcov.hip.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -36,44 +37,17 @@
 #include <unordered_map>
 #include <vector>
 #include "lmat_internal.hpp"
+#include "kmer_dev.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef uint32_t u32;
+using namespace lmat_dev;   // kmer_dev.hpp: the wave helpers, the two phases of the text scan, DevBuf, with_temp, LapTimer
 
-constexpr int kSpan = 992;        // window ends one wave covers: 62 blocks of 16 bases, behind 2 blocks (32 bases >= k - 1) of lead-in
-constexpr int kLead = 32;         // bytes of text in front of a chunk (the k - 1 overlap, rounded up to the 16-byte loads)
-constexpr int kWavesPerBlock = 4;
 constexpr u32 kNoNode = 0xFFFFFFFFu;
 constexpr u32 kMaxList = 65535;   // the record's count field is 16 bits wide (tax_histo.cpp:258-259)
 
 // counters of one pass (device, 64-bit words)
 enum { C_CURSOR = 0, C_OVERFLOW, C_WINDOWS, C_DROPPED, C_SINGLETONS, C_ENTRIES, C_LONGEST, C_TOOLONG, C_LONG_RUNS, C_LONG_ENTRIES, C_N };
-
-__device__ __forceinline__ u32 lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-// the memory of the wave's own LDS / global writes made visible to its other lanes
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-template <class T, class Op> __device__ __forceinline__ T wave_reduce(T v, Op op) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = op(v, (T)__shfl_xor(v, d));
-    return v;
-}
-template <class T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T x, T y) { return x + y; }); }
-template <class T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, [](T x, T y) { return x > y ? x : y; }); }
-
-// reverse complement of a k-mer held in the low 2k bits (Encoder::rc): 2-bit groups reversed, complemented
-__device__ __forceinline__ u64 revcomp(u64 x, int k) {
-    u64 r = __brevll(x);
-    r = ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
-    return (~r) >> (64 - 2 * k);
-}
 
 struct ExtractArgs {
     const uint8_t* buf;      // chunk bytes: buf[kLead + i] = text[chunk_lo + i]; every wave's 1024-byte window is allocated and filled
@@ -90,11 +64,8 @@ struct ExtractArgs {
     u64* counters;
 };
 
-// Every wave covers kSpan consecutive window ends.  Phase 1: lane l packs the 16 bases at byte 16 l of the wave's 1024-byte
-// window into one 32-bit word (first base in the high bits) and a mask of its invalid bytes; an inclusive max-scan over the
-// lanes gives, per block, the last invalid byte at or before its end.  Phase 2: lane l of step s takes the window that ends at
-// byte 32 + 64 s + l: the run of valid bases that ends there is the distance to the last invalid byte (the scan's value of the
-// block before + the own block's mask), the k-mer is 2k bits cut from three packed words.
+// Every wave covers kSpan consecutive window ends.  Phase 1 (pack_span): the wave's 1024-byte window packed into LDS.  Phase 2: lane l
+// of step s takes the window that ends at byte 32 + 64 s + l (window_kmer).  Both phases are kmer_dev.hpp's, shared with kcov.hip.
 __global__ __launch_bounds__(64 * kWavesPerBlock) void extract_kernel(ExtractArgs a) {
     __shared__ u32 s_word[kWavesPerBlock][64];
     __shared__ int s_last[kWavesPerBlock][64];
@@ -104,43 +75,13 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void extract_kernel(ExtractArg
     const u64 wave = (u64)blockIdx.x * kWavesPerBlock + wv;
     const u64 wbase = wave * kSpan;               // first window end of the wave, relative to the chunk
     if (wbase >= a.chunk_len) return;             // whole waves only: no block-wide barrier below
-    {
-        const uint4 q = *reinterpret_cast<const uint4*>(a.buf + wbase + 16 * lane);
-        const u32 w4[4] = {q.x, q.y, q.z, q.w};
-        u32 word = 0, inv = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const u32 c = (w4[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-            const u32 up = (c & 0xDFu) - 0x41u;                              // 'A' -> 0, 'C' -> 2, 'G' -> 6, 'T' -> 19
-            const bool ok = up < 20u && ((0x80045u >> up) & 1u);
-            const u32 code = ((c >> 1) ^ (c >> 2)) & 3u;                     // A 0, C 1, G 2, T 3
-            word |= code << (30 - 2 * j);
-            inv |= (ok ? 0u : 1u) << j;
-        }
-        int last = inv ? (int)(16 * lane) + 31 - __clz((int)inv) : -1;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(last, d);
-            if ((int)lane >= d) last = max(last, o);
-        }
-        s_word[wv][lane] = word;
-        s_inv[wv][lane] = inv;
-        s_last[wv][lane] = last;
-    }
+    pack_span(a.buf + wbase, lane, s_word[wv], s_inv[wv], s_last[wv]);
     wave_sync();
     const int k = a.k;
     const u64 kmask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
     // the records this wave's span can touch
     u32 rlo, rhi;
-    {
-        const u64 p0 = a.chunk_lo + wbase, p1 = p0 + kSpan - 1;
-        u32 lo = 0, hi = a.n_rec;
-        while (lo < hi) { const u32 m = (lo + hi) >> 1; if (a.rec_start[m] <= p0) lo = m + 1; else hi = m; }
-        rlo = lo ? lo - 1 : 0;
-        hi = a.n_rec;
-        while (lo < hi) { const u32 m = (lo + hi) >> 1; if (a.rec_start[m] <= p1) lo = m + 1; else hi = m; }
-        rhi = lo;   // records [rlo, rhi)
-    }
+    span_records(a.rec_start, a.n_rec, a.chunk_lo + wbase, a.chunk_lo + wbase + kSpan - 1, rlo, rhi);
     u64 n_windows = 0;
     for (int step = 0; step * 64 < kSpan; ++step) {
         const u32 q = step * 64 + lane;            // window end within the span
@@ -148,15 +89,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void extract_kernel(ExtractArg
         bool emit = false;
         u64 canon = 0;
         if (q < (u32)kSpan && wbase + q < a.chunk_len) {
-            const u32 bt = t >> 4, in = t & 15u;
-            const u32 m = s_inv[wv][bt] & ((2u << in) - 1u);
-            const int last = m ? (int)(16 * bt) + 31 - __clz((int)m) : s_last[wv][bt - 1];
-            if ((int)t - last >= k) {
-                const u64 lo = ((u64)s_word[wv][bt - 1] << 32) | s_word[wv][bt];
-                const unsigned __int128 x = ((unsigned __int128)s_word[wv][bt - 2] << 64) | lo;
-                const u64 fwd = (u64)(x >> (2 * (15 - in))) & kmask;
-                const u64 rc = revcomp(fwd, k);
-                canon = fwd < rc ? fwd : rc;
+            if (window_kmer(s_word[wv], s_inv[wv], s_last[wv], t, k, kmask, canon)) {
                 emit = a.prefix_bits == 0 || (u32)(canon >> (2 * k - a.prefix_bits)) == a.pass;
                 n_windows += 1;
             }
@@ -171,9 +104,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void extract_kernel(ExtractArg
                 if (lane == 0) atomicMax(&a.counters[C_OVERFLOW], 1ull);   // the pass is repeated or refused by the host, never cut short
             } else if (emit) {
                 const u64 pos = a.chunk_lo + wbase + q;
-                u32 lo = rlo, hi = rhi;              // last record that starts at or before pos
-                while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (a.rec_start[mid] <= pos) lo = mid; else hi = mid; }
-                const u32 owner = a.rec_owner[lo];
+                const u32 owner = a.rec_owner[record_at(a.rec_start, rlo, rhi, pos)];
                 const u64 dst = base + __popcll(bal & ((1ull << lane) - 1));
                 if (a.owner_bits >= 0) a.keys[dst] = (canon << a.owner_bits) | owner;
                 else { a.keys[dst] = canon; a.vals[dst] = owner; }
@@ -637,57 +568,6 @@ __global__ __launch_bounds__(256) void hist_kernel(const u32* tids, u64 n, const
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t ensure(size_t n) {
-        if (n <= bytes && p) return hipSuccess;
-        if (p) { hipFree(p); p = nullptr; bytes = 0; }
-        hipError_t e = hipMalloc(&p, std::max<size_t>(n, 256));
-        if (e == hipSuccess) bytes = std::max<size_t>(n, 256);
-        return e;
-    }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-hipError_t ensure_all(std::initializer_list<std::pair<DevBuf*, size_t>> need) {   // (buffer, bytes) ...
-    for (const auto& n : need)
-        if (const hipError_t e = n.first->ensure(n.second)) return e;
-    return hipSuccess;
-}
-
-// rocPRIM's two calls: without storage it reports the bytes it needs, with them it runs.  call(void* storage, size_t& bytes)
-template <class Call> hipError_t with_temp(DevBuf& temp, Call call) {
-    size_t bytes = 0;
-    hipError_t e = call(nullptr, bytes);
-    if (e == hipSuccess) e = temp.ensure(bytes);
-    if (e == hipSuccess) e = call(temp.p, bytes);
-    return e;
-}
-
-// HIP-event time on the stream, stage by stage: lap() adds the ms since start() or the lap before it
-struct LapTimer {
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~LapTimer() { if (ev[0]) hipEventDestroy(ev[0]); if (ev[1]) hipEventDestroy(ev[1]); }
-    hipError_t init(hipStream_t s) {
-        st = s;
-        const hipError_t e = hipEventCreate(&ev[0]);
-        return e == hipSuccess ? hipEventCreate(&ev[1]) : e;
-    }
-    hipError_t start() { return hipEventRecord(ev[0], st); }
-    hipError_t lap(float& acc) {
-        hipError_t e = hipEventRecord(ev[1], st);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        acc += ms;
-        if (e == hipSuccess) e = hipEventRecord(ev[0], st);
-        return e;
-    }
-};
-
 struct LongBufs {   // the side buffers of the lists beyond 64 entries
     DevBuf tmp, sorted, begin, end, run;
     LongArgs args() const { return LongArgs{tmp.as<u32>(), begin.as<u32>(), end.as<u32>(), run.as<u32>()}; }
