@@ -55,8 +55,8 @@ int nccl_err(lmat_ctx* c, const char* what, ncclResult_t e) {
 // Queued launches leave their last kernels -- which add to the tallies -- on the context's side streams (LMAT_PIPELINE): the
 // merge is ordered behind them here, whatever the caller did or did not wait for.
 void order_behind_launches(lmat_ctx* c) {
-    if (c->set_in_flight && c->ev_done) hipStreamWaitEvent(c->stream, c->ev_done, 0);
-    if (c->parked.in_flight && c->parked.done) hipStreamWaitEvent(c->stream, c->parked.done, 0);
+    for (const auto& s : c->sets)
+        if (s.in_flight && s.done) hipStreamWaitEvent(c->stream, s.done, 0);
 }
 // the three arrays of a tally buffer, queued on the context's stream (inside a group)
 ncclResult_t queue_tallies(Rccl& R, lmat_ctx* c, ncclComm_t comm) {

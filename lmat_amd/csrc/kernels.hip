@@ -4055,7 +4055,7 @@ void launch_k4_begin(const ClassifyArgs& a, hipStream_t stream, hipStream_t stre
     hipEventRecord(forked, stream);
     hipStreamWaitEvent(stream2, forked, 0);
     ClassifyArgs b = a;
-    b.k4_slot = 5;
+    b.k4_slot = kCurK4Large;
     const uint64_t waves = (a.count + 63) / 64;
     uint64_t g2 = waves < 256 * 32 ? waves : 256 * 32;
     if (g2 < 1) g2 = 1;
@@ -4070,7 +4070,7 @@ void launch_k4_begin(const ClassifyArgs& a, hipStream_t stream, hipStream_t stre
     } else if (mode == 1) {
         launch_k4_lds<kK4MidT>(a, a.count, stream2);
     } else {
-        b.k4_slot = 8;
+        b.k4_slot = kCurK4Mid;
         k4_kernel<false, kK4MidT, 64><<<dim3((unsigned)g2), dim3(64), 0, stream2>>>(b);
     }
     hipStreamWaitEvent(stream3, forked, 0);
@@ -4096,7 +4096,7 @@ void launch_k4_end(const ClassifyArgs& a, hipStream_t join_stream, hipStream_t s
         hipStreamWaitEvent(join_stream, joined_small, 0);
     }
     ClassifyArgs b = a;
-    b.k4_slot = 6;  // the few reads whose lineage outgrew a tier's block
+    b.k4_slot = kCurK4Bail;  // the few reads whose lineage outgrew a tier's block
     if (a.nm.active) k4_kernel<true, kK4T, 64><<<dim3(64), dim3(64), 0, join_stream>>>(b);
     else k4_kernel<false, kK4T, 64><<<dim3(64), dim3(64), 0, join_stream>>>(b);
     hipEventRecord(done, join_stream);

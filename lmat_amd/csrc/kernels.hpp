@@ -16,14 +16,14 @@ struct ClassifyArgs {
     lmat_read_result* results;
     lmat_cand* cands;          // may be null (calls-only)
     uint64_t cand_cap;
-    uint32_t* cursor;          // per-batch counters: [0] candidate bump cursor, [2..] list lengths; behind the 16 words: kCandSubs sub-cursors (64 B apart)
+    uint32_t* cursor;          // per-batch counters (CursorWord below); behind the 16 words: kCandSubs sub-cursors (64 B apart)
     uint32_t cand_chunk = 0;   // pairs a sub-cursor takes from the bump cursor at a time (0: every read bumps the cursor itself)
     uint32_t cand_sub_mask = 0; // sub-cursors in use - 1 (a power of two, at most kCandSubs: fewer for smaller batches, whose slack would otherwise outweigh their pairs)
     uint32_t* err;             // sticky error flags: launches only OR into the word
     void* counts;              // u64 count[n_ids] | f64 score[n_ids] | u64 nomatch[3]
     uint32_t phix_call_idx;    // internal index of 32630
     uint32_t* ovf_list;        // reads that exceed this launch's capacities are appended here (count in cursor[ovf_slot])
-    uint32_t ovf_slot;         // cursor word that counts ovf_list: 2 fast -> E=512 class, 3 -> middle tier, 10 -> large LDS class, 7 -> global-memory class
+    uint32_t ovf_slot;         // cursor word that counts ovf_list: one of kCurOvf*
     const uint32_t* count_ptr; // when set, the number of `index` entries is read from device memory
     uint32_t* k4buf;           // per-read records handed from the fast classify kernel to the K4 kernels
     uint32_t* k4_small;        // read indices awaiting K4, small tables (count in cursor[4])
@@ -31,7 +31,7 @@ struct ClassifyArgs {
     uint32_t* k4_large;        // read indices awaiting K4, large tables (count in cursor[5])
     uint32_t* k4_bail;         // reads the LDS K4 kernel could not hold after all (count in cursor[6])
     uint32_t* k4_row;          // read indices awaiting k4_row_kernel: up to 16 taxids, decision by rows (count in cursor[9])
-    uint32_t k4_slot;          // which of the two lists a k4_kernel launch takes (5 or 6)
+    uint32_t k4_slot;          // which list a k4_kernel launch takes: kCurK4Large, kCurK4Mid or kCurK4Bail
     // rand_read_label mode (null-model generation): per (taxid, GC bucket) the largest k-mer fraction over the reads and
     // the number of reads that hit the taxid; the decision step is skipped
     uint32_t* rand_max;        // [n_ids][rand_nb] float bits, or null
@@ -61,6 +61,20 @@ static const int kK4RecWords = 2 + kK4T;
 static const int kCandSubs = 1024;
 static const int kCursorWords = 16;   // the counter block proper
 static const size_t kCursorBytes = kCursorWords * 4 + (size_t)kCandSubs * 64;
+// words of the counter block (ClassifyArgs::cursor); every launch starts with all of them zero
+enum CursorWord {
+    kCurCand = 0,       // candidate bump cursor
+    kCurOvfFast = 2,    // length of the list of reads the fast classes passed on (to the E = 512 class)
+    kCurOvfE512 = 3,    // ... the E = 512 class passed on (to the middle tier, or the large LDS class)
+    kCurOvfMid = 10,    // ... the middle tier passed on (to the large LDS class)
+    kCurOvfLarge = 7,   // ... the large LDS class passed on (to the global-memory class)
+    kCurK4Small = 4,    // reads awaiting K4 by table size (k4_compact_kernel): small tables,
+    kCurK4Large = 5,    // large tables,
+    kCurK4Mid = 8,      // up to 32 taxids,
+    kCurK4Row = 9,      // up to 16 taxids, decided by rows (LMAT_K4_ROW);
+    kCurK4Bail = 6,     // reads a K4 kernel could not hold after all
+    kCurBatchErr = 15,  // error flags of a batch that keeps its own (the streamed boundary) instead of the sticky word
+};
 
 enum { kErrTidOverflow = 1, kErrReadTooLong = 2, kErrCandOverflow = 4, kErrLineageTrunc = 8, kErrNoNullModel = 16 };
 

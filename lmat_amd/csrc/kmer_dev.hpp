@@ -1,14 +1,13 @@
 // kmer_dev.hpp -- what the k-mer pipelines on the device share (dbgen.hip: the database builder; kcov.hip: the per-group k-mer coverage).
 //   device: the wave helpers and the two phases of the text scan -- a wave's 1024 bytes packed into LDS (pack_span), the canonical
 //           k-mer of the window that ends at one byte of them (window_kmer) -- and the record of a text position (span_records / record_at);
-//   host:   DevBuf, ensure_all, with_temp (rocPRIM's two calls) and LapTimer (HIP-event time per stage).
+//   host:   with_temp (rocPRIM's two calls) and LapTimer (HIP-event time per stage); DevBuf and ensure_all come from devbuf.hpp.
 // Included by HIP translation units only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
-#include <initializer_list>
-#include <utility>
+#include "devbuf.hpp"
 
 namespace lmat_dev {
 
@@ -104,26 +103,6 @@ __device__ __forceinline__ u32 record_at(const u64* rec_start, u32 lo, u32 hi, u
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t ensure(size_t n) {
-        if (n <= bytes && p) return hipSuccess;
-        if (p) { hipFree(p); p = nullptr; bytes = 0; }
-        hipError_t e = hipMalloc(&p, std::max<size_t>(n, 256));
-        if (e == hipSuccess) bytes = std::max<size_t>(n, 256);
-        return e;
-    }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-inline hipError_t ensure_all(std::initializer_list<std::pair<DevBuf*, size_t>> need) {   // (buffer, bytes) ...
-    for (const auto& n : need)
-        if (const hipError_t e = n.first->ensure(n.second)) return e;
-    return hipSuccess;
-}
-
 // rocPRIM's two calls: without storage it reports the bytes it needs, with them it runs.  call(void* storage, size_t& bytes)
 template <class Call> hipError_t with_temp(DevBuf& temp, Call call) {
     size_t bytes = 0;

@@ -77,7 +77,6 @@ int upload_taxonomy(lmat_ctx* c) {
         if (T.path_len[i] && T.fdepth[i] <= T.fdepth[T.paths[T.path_off[i]]]) { c->dev.depth_consistent = 0; break; }
     // tallies: u64 count[n_ids] | f64 score[n_ids] | u64 nomatch[3]
     if (c->d_counts) { hipFree(c->d_counts); c->d_counts = nullptr; }
-    if (c->d_counts_bak) { hipFree(c->d_counts_bak); c->d_counts_bak = nullptr; }
     c->counts_bytes = (uint64_t)c->dev.n_ids * 16 + 24;
     HIPCHK(c, hipMalloc(&c->d_counts, c->counts_bytes));
     HIPCHK(c, hipMemset(c->d_counts, 0, c->counts_bytes));
@@ -125,10 +124,9 @@ int lmat_ctx_create(int device, const lmat_params* params, lmat_ctx** out) {
     lmat_params def = {1.0f, 3.0f, 0.0f, 35, 1, 0, 1};
     c->params = params ? *params : def;
     if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return LMAT_E_DEVICE; }
-    if (hipMalloc((void**)&c->d_cursor, kCursorBytes) != hipSuccess || hipMalloc((void**)&c->parked.d_cursor, kCursorBytes) != hipSuccess ||
+    if (c->sets[0].cursor.ensure(kCursorBytes) != hipSuccess || c->sets[1].cursor.ensure(kCursorBytes) != hipSuccess ||
         hipMalloc((void**)&c->d_err, 64) != hipSuccess) { delete c; return LMAT_E_DEVICE; }
-    hipMemset(c->d_cursor, 0, kCursorBytes);
-    hipMemset(c->parked.d_cursor, 0, kCursorBytes);
+    for (auto& s : c->sets) hipMemset(s.cursor.p, 0, kCursorBytes);
     hipMemset(c->d_err, 0, 64);
     *out = c;
     return LMAT_OK;
@@ -141,10 +139,8 @@ void lmat_ctx_destroy(lmat_ctx* c) {
     for (auto& e : c->pending_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto& e : c->pending_events2) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     void* ptrs[] = {c->dev.slots, c->dev.ovf_slots, c->dev.arena, c->dev.tid32, c->dev.fdepth, c->dev.flags, c->dev.species_of,
-                    c->dev.path_off, c->dev.path_len, c->dev.paths, c->dev.paths8, c->dev.paths_fl, c->dev.facts16, c->dev.conv, c->dev.tin, c->dev.tout, c->dev.paths32, c->dev.tin32, c->dev.tout32, c->dev.species_of32, c->d_results, c->d_cands, c->d_cursor,
-                    c->d_counts, c->d_counts_bak, c->d_synth_strain_idx, c->d_ovf, c->d_ovf2, c->d_ovf3, c->d_ovf4, c->parked.d_ovf4, c->d_k4buf, c->d_k4small, c->d_k4large, c->d_k4bail, c->d_tail, c->parked.d_tail, c->d_gscratch, c->d_rand_max, c->d_rand_cnt, c->d_rand_gc,
-                    c->d_err, c->parked.d_results, c->parked.d_cands, c->parked.d_cursor, c->parked.d_ovf, c->parked.d_ovf2, c->parked.d_ovf3, c->parked.d_k4buf, c->parked.d_k4small,
-                    c->parked.d_k4large, c->parked.d_k4bail};
+                    c->dev.path_off, c->dev.path_len, c->dev.paths, c->dev.paths8, c->dev.paths_fl, c->dev.facts16, c->dev.conv, c->dev.tin, c->dev.tout, c->dev.paths32, c->dev.tin32, c->dev.tout32, c->dev.species_of32,
+                    c->d_counts, c->d_synth_strain_idx, c->d_rand_max, c->d_rand_cnt, c->d_err};   // (the batch sets and the other DevBufs free themselves)
     for (void* p : ptrs)
         if (p) hipFree(p);
     sb_free(c);
@@ -153,9 +149,7 @@ void lmat_ctx_destroy(lmat_ctx* c) {
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->ev_join) hipEventDestroy(c->ev_join);
     if (c->ev_join3) hipEventDestroy(c->ev_join3);
-    if (c->ev_done) hipEventDestroy(c->ev_done);
     if (c->ev_join_small) hipEventDestroy(c->ev_join_small);
-    if (c->parked.done) hipEventDestroy(c->parked.done);
     if (c->stream3) hipStreamDestroy(c->stream3);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -1238,15 +1232,6 @@ int lmat_synth_read_windows(lmat_ctx* c, const uint32_t* lengths, uint32_t n_len
 }
 
 // ---------------------------------------------------------------------------------- reads
-// The fast kernel's capacity class follows the bulk of the batch, not its longest read: the length below which
-// 99 % of the reads fall; longer ones are re-run by a larger class through the device-side overflow list.
-static uint32_t bulk_length(std::vector<uint32_t>& lens) {
-    if (lens.empty()) return 0;
-    const size_t kth = (size_t)((lens.size() - 1) * 0.99);
-    std::nth_element(lens.begin(), lens.begin() + kth, lens.end());
-    return lens[kth];
-}
-
 static int reads_alloc(lmat_ctx* c, const std::vector<uint64_t>& rec_off, uint32_t max_len, lmat_reads** out) {
     lmat_reads* r = new lmat_reads();
     r->n = rec_off.size() - 1;
@@ -1279,7 +1264,6 @@ int lmat_reads_upload(lmat_ctx* c, const uint8_t* bases, const uint64_t* off, ui
     int rc = reads_alloc(c, rec_off, max_len, out);
     if (rc) return rc;
     (*out)->lens = lens;
-    (*out)->class_len = bulk_length(lens);
     if (!n) return LMAT_OK;
     uint8_t* d_b = nullptr;
     uint64_t* d_o = nullptr;
@@ -1310,7 +1294,6 @@ int lmat_reads_synth(lmat_ctx* c, uint64_t n, const uint32_t* lengths, uint32_t 
     }
     int rc = reads_alloc(c, rec_off, max_len, out);
     if (rc) return rc;
-    (*out)->class_len = max_len;  // a handful of configured lengths: no tail to cut
     (*out)->lens.swap(lens);
     uint32_t* d_len = nullptr;
     HIPCHK(c, hipMalloc((void**)&d_len, n_lengths * 4));
@@ -1358,51 +1341,26 @@ void lmat_reads_free(lmat_ctx* c, lmat_reads* r) {
 }
 
 // ---------------------------------------------------------------------------------- classify
-static int ensure_results(lmat_ctx* c, uint64_t count, uint64_t cand_cap) {
-    if (count > c->results_cap) {
-        if (c->d_results) hipFree(c->d_results);
-        c->d_results = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->d_results, count * sizeof(lmat_read_result)));
-        c->results_cap = count;
-    }
-    if (cand_cap > c->cands_cap) {
-        if (c->d_cands) hipFree(c->d_cands);
-        c->d_cands = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->d_cands, cand_cap * sizeof(lmat_cand)));
-        c->cands_cap = cand_cap;
-    }
+using lmat_dev::DevBuf;
+typedef lmat_ctx::BatchSet BatchSet;
+
+static int ensure_results(lmat_ctx* c, BatchSet& s, uint64_t count, uint64_t cand_cap) {
+    if (count) HIPCHK(c, s.results.ensure(count * sizeof(lmat_read_result)));
+    if (cand_cap) HIPCHK(c, s.cands.ensure(cand_cap * sizeof(lmat_cand)));
     return LMAT_OK;
 }
-// per-batch scratch of the kernels (overflow lists, the K4 hand-off records): sized by the largest batch so far
-static int ensure_scratch(lmat_ctx* c, uint64_t count) {
-    if (count > c->ovf_cap) {
-        if (c->d_ovf) hipFree(c->d_ovf);
-        if (c->d_k4buf) hipFree(c->d_k4buf);
-        c->d_ovf = nullptr;
-        c->d_k4buf = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->d_k4buf, count * (uint64_t)kK4RecWords * sizeof(uint32_t)));
-        if (c->d_k4small) hipFree(c->d_k4small);
-        if (c->d_k4large) hipFree(c->d_k4large);
-        c->d_k4small = c->d_k4large = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->d_k4small, count * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_k4large, 3 * count * sizeof(uint32_t)));  // three lists: large tables | up to 32 taxids | up to 16, by rows
-        if (c->d_k4bail) hipFree(c->d_k4bail);
-        c->d_k4bail = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->d_k4bail, count * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_ovf, count * sizeof(uint32_t)));
-        if (c->d_ovf2) hipFree(c->d_ovf2);
-        if (c->d_ovf3) hipFree(c->d_ovf3);
-        if (c->d_ovf4) hipFree(c->d_ovf4);
-        c->d_ovf2 = c->d_ovf3 = c->d_ovf4 = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->d_ovf2, count * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_ovf3, count * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_ovf4, count * sizeof(uint32_t)));
-        c->ovf_cap = count;
-    }
+// per-batch scratch of the kernels (overflow lists, the K4 hand-off records and lists): sized by the largest batch so far
+static int ensure_scratch(lmat_ctx* c, BatchSet& s, uint64_t count) {
+    if (count <= s.scratch_reads) return LMAT_OK;
+    s.scratch_reads = 0;
+    const size_t list = count * sizeof(uint32_t);
+    HIPCHK(c, lmat_dev::ensure_all({{&s.k4buf, list * kK4RecWords}, {&s.k4small, list}, {&s.k4large, 3 * list}, {&s.k4bail, list},
+                                    {&s.ovf[0], list}, {&s.ovf[1], list}, {&s.ovf[2], list}, {&s.ovf[3], list}}));
+    s.scratch_reads = count;
     return LMAT_OK;
 }
 
-static ClassifyArgs make_args(lmat_ctx* c, const lmat_reads* reads, uint64_t first, uint64_t count, bool want_cands,
+static ClassifyArgs make_args(lmat_ctx* c, const BatchSet& s, const lmat_reads* reads, uint64_t first, uint64_t count, bool want_cands,
                               uint64_t cand_cap) {
     ClassifyArgs a;
     a.tb = c->dev;
@@ -1414,8 +1372,8 @@ static ClassifyArgs make_args(lmat_ctx* c, const lmat_reads* reads, uint64_t fir
     a.first = first;
     a.count = count;
     a.result_base = first;
-    a.results = c->out_results ? c->out_results : c->d_results;
-    a.cands = want_cands ? (c->out_cands ? c->out_cands : c->d_cands) : nullptr;
+    a.results = c->out_results ? c->out_results : s.results.as<lmat_read_result>();
+    a.cands = want_cands ? (c->out_cands ? c->out_cands : s.cands.as<lmat_cand>()) : nullptr;
     a.cand_cap = cand_cap;
     // Large candidate buffers are handed out through sub-cursors, a chunk at a time (kernels.hpp): at most kCandSubs chunks lie
     // partly unused at the end of a launch, an eighth of the buffer in the worst case.  Small ones -- few reads, no contention --
@@ -1436,43 +1394,31 @@ static ClassifyArgs make_args(lmat_ctx* c, const lmat_reads* reads, uint64_t fir
         a.cand_chunk = (uint32_t)ch;
         a.cand_sub_mask = subs - 1;
     }
-    a.cursor = c->d_cursor;
-    a.err = c->batch_err ? c->d_cursor + 15 : c->d_err;  // a streamed batch keeps its own flags (word 15 of the per-batch counter block)
+    a.cursor = s.word(0);
+    a.err = c->batch_err ? s.word(kCurBatchErr) : c->d_err;  // a streamed batch keeps its own flags in its counter block
     a.counts = c->out_counts ? c->out_counts : c->d_counts;
     auto it = c->tax.index_of.find(32630);
     a.phix_call_idx = it == c->tax.index_of.end() ? 0 : it->second;
-    a.ovf_list = c->d_ovf;
-    a.ovf_slot = 2;
+    a.ovf_list = s.ovf[0].as<uint32_t>();
+    a.ovf_slot = kCurOvfFast;
     a.count_ptr = nullptr;
-    a.k4buf = c->d_k4buf;
+    a.k4buf = s.k4buf.as<uint32_t>();
     a.gscratch = nullptr;
     a.rand_max = nullptr;
     a.rand_cnt = nullptr;
     a.rand_gc = nullptr;
     a.rand_nb = 0;
-    if (c->rand_launch) { a.rand_max = c->d_rand_max; a.rand_cnt = c->d_rand_cnt; a.rand_gc = c->d_rand_gc; a.rand_nb = c->rand_nb; }
-    a.k4_small = c->d_k4small;
-    a.k4_large = c->d_k4large;
-    a.k4_mid = c->d_k4large + c->ovf_cap;
-    a.k4_row = c->d_k4large + 2 * c->ovf_cap;
-    a.k4_bail = c->d_k4bail;
-    a.k4_slot = 5;
+    if (c->rand_launch) { a.rand_max = c->d_rand_max; a.rand_cnt = c->d_rand_cnt; a.rand_gc = c->rand_gc.as<uint8_t>(); a.rand_nb = c->rand_nb; }
+    a.k4_small = s.k4small.as<uint32_t>();
+    a.k4_large = s.k4large.as<uint32_t>();
+    a.k4_mid = a.k4_large + s.scratch_reads;
+    a.k4_row = a.k4_large + 2 * s.scratch_reads;
+    a.k4_bail = s.k4bail.as<uint32_t>();
+    a.k4_slot = kCurK4Large;
     a.nm = c->nm;
     a.gene_mode = (uint32_t)c->gene_mode;
     if (c->gene_mode) a.prm.min_kmer = 0;  // gene_label looks every read of >= k bases up (gene_label.cpp:276-288)
     return a;
-}
-
-// the set of per-batch buffers in use <-> the parked one
-static void swap_sets(lmat_ctx* c) {
-    auto& p = c->parked;
-    std::swap(c->d_results, p.d_results); std::swap(c->results_cap, p.results_cap);
-    std::swap(c->d_cands, p.d_cands); std::swap(c->cands_cap, p.cands_cap);
-    std::swap(c->d_cursor, p.d_cursor); std::swap(c->d_ovf, p.d_ovf); std::swap(c->d_ovf2, p.d_ovf2); std::swap(c->d_ovf3, p.d_ovf3); std::swap(c->d_ovf4, p.d_ovf4);
-    std::swap(c->d_k4buf, p.d_k4buf); std::swap(c->d_k4small, p.d_k4small); std::swap(c->d_k4large, p.d_k4large);
-    std::swap(c->d_k4bail, p.d_k4bail); std::swap(c->ovf_cap, p.ovf_cap);
-    std::swap(c->d_tail, p.d_tail); std::swap(c->tail_bytes, p.tail_bytes);
-    std::swap(c->ev_done, p.done); std::swap(c->set_in_flight, p.in_flight);
 }
 
 // Queued launches (lmat_classify_async, the streamed boundary) take the two sets of per-batch buffers in turn, and what follows
@@ -1485,6 +1431,147 @@ static bool pipeline_on() {
     static const bool on = !getenv("LMAT_PIPELINE") || atoi(getenv("LMAT_PIPELINE")) != 0;
     return on;
 }
+
+static int err_read_too_long(lmat_ctx* c) {
+    return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
+}
+
+// ---- the stages of a launch (run_classify below), in their order ----
+
+// The set: a pipelined launch takes the other one; its previous batch has to be through before the buffers are sized for this
+// one (DevBuf::ensure: a regrown buffer is freed first) and the counters cleared.
+static int prepare_set(lmat_ctx* c, uint64_t count, bool want_cands, uint64_t cand_cap, bool pipelined) {
+    if (pipelined) c->cur_set ^= 1;
+    BatchSet& s = c->set();
+    if (!s.done) HIPCHK(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (s.in_flight) HIPCHK(c, hipStreamWaitEvent(c->stream, s.done, 0));
+    int rc = ensure_results(c, s, c->out_results ? 0 : count, want_cands && !c->out_cands ? cand_cap : 0);
+    if (!rc) rc = ensure_scratch(c, s, count);
+    if (rc) return rc;
+    HIPCHK(c, c->gscratch.ensure(classify_gmem_scratch_bytes()));  // per-read tables of the global-memory class (very long reads, very large taxid tables)
+    // per-launch counters: the candidate cursor and the list lengths; the error word (d_err) is sticky -- launches
+    // only OR into it and whoever reports it (lmat_sync, lmat_classify, lmat_rand_label) clears it
+    HIPCHK(c, hipMemsetAsync(s.cursor.p, 0, want_cands ? kCursorBytes : (size_t)kCursorWords * 4, c->stream));  // (the sub-cursors start empty: next free = end = 0)
+    return LMAT_OK;
+}
+
+// Tails (tail_kernel): where the reads of the 160-k-mer class end a few positions past their second chunk -- 150 bp reads
+// at k = 20 have 131 -- those positions are looked up beforehand, 4, 8 or 16 lanes per read.  Compact layout, no null
+// models (their GC accounting walks every chunk).  LMAT_TAIL=0 turns it off.
+// single_class: the whole batch runs in the class its longest read asks for.
+static void plan_tail(lmat_ctx* c, BatchSet& s, const lmat_reads* reads, bool single_class, ClassifyArgs& a) {
+    static const bool tail_on = !getenv("LMAT_TAIL") || atoi(getenv("LMAT_TAIL")) != 0;
+    static const int tail_force = getenv("LMAT_TAIL_LPR") ? atoi(getenv("LMAT_TAIL_LPR")) : 0;  // experiments: 4, 8 or 16
+    const uint32_t k = (uint32_t)c->dev.k;
+    const uint32_t realP = reads->max_len >= k ? reads->max_len - k + 1 : 0;
+    if (single_class && realP > 160u) return;
+    const uint32_t maxP = std::min<uint32_t>(realP, 160u);
+    uint32_t lpr = 0;
+    if (tail_on && c->dev.cpt.nb && !c->nm.active && maxP > 128u) lpr = maxP <= 132u ? 4u : (maxP <= 136u ? 8u : 16u);
+    if (lpr && (tail_force == 4 || tail_force == 8 || tail_force == 16) && 128u + (uint32_t)tail_force >= std::min(maxP, 144u)) lpr = (uint32_t)tail_force;
+    if (!lpr) return;
+    if (s.tail.ensure(a.count * (16ull * lpr + 32ull)) != hipSuccess) { (void)hipGetLastError(); return; }  // no room for them: the reads run their third chunk
+    a.tail_lpr = lpr;
+    a.tail16 = s.tail.as<uint32_t>();
+    a.tail_u = (const uint64_t*)(s.tail.as<unsigned char>() + a.count * 16ull * lpr);
+}
+
+// Length classes of a read set uploaded whole (lmat_reads_upload / lmat_reads_synth): built on first use for the database's k,
+// on the device only when the set spans more than one class.
+static int build_class_lists(lmat_ctx* c, lmat_reads* rw) {
+    const uint32_t k = (uint32_t)c->dev.k;
+    if (rw->preset || rw->cls_k == (int)k || rw->lens.size() != rw->n) return LMAT_OK;
+    for (int j = 0; j < kNCls; ++j) { rw->cls_host[j].clear(); if (rw->cls_dev[j]) { hipFree(rw->cls_dev[j]); rw->cls_dev[j] = nullptr; } }
+    for (uint64_t i = 0; i < rw->n; ++i) {
+        const uint32_t P = rw->lens[i] >= k ? rw->lens[i] - k + 1 : 0;
+        rw->cls_host[len_class(P)].push_back((uint32_t)i);
+    }
+    int used = 0;
+    for (int j = 0; j < kNCls; ++j) used += !rw->cls_host[j].empty();
+    if (used > 1)
+        for (int j = 0; j < kNCls; ++j)
+            if (!rw->cls_host[j].empty()) {
+                HIPCHK(c, hipMalloc((void**)&rw->cls_dev[j], rw->cls_host[j].size() * 4));
+                HIPCHK(c, hipMemcpyAsync(rw->cls_dev[j], rw->cls_host[j].data(), rw->cls_host[j].size() * 4, hipMemcpyHostToDevice, c->stream));
+            }
+    rw->cls_k = (int)k;
+    return LMAT_OK;
+}
+
+// The reads of a batch that one fast class takes: index == nullptr is the batch as it stands (first + i).
+struct ClassSpan { const uint32_t* index; uint64_t count; uint32_t max_len; bool tail; };
+// Each read runs in the smallest fast class that holds it (160 / 256 / 320 / 512 k-mers; 512 = 531 bp at k = 20); longer
+// reads ride the overflow list to the wave-per-read classes behind it.  The spans come from the lists a stream slot brings
+// along (over the whole batch, already on the device), from the read set's own lists, or -- one class only -- are the batch itself.
+static int class_spans(const lmat_ctx* c, const lmat_reads* r, uint64_t first, uint64_t count, ClassSpan out[kNCls]) {
+    const uint32_t k = (uint32_t)c->dev.k;
+    const bool mixed = r->cls_dev[0] || r->cls_dev[1] || r->cls_dev[2] || r->cls_dev[3];
+    int n = 0;
+    for (int j = 0; j < kNCls; ++j) {
+        uint64_t lo = 0, hi = 0;
+        if (r->preset) hi = r->cls_n[j];
+        else if (mixed) {
+            const std::vector<uint32_t>& v = r->cls_host[j];
+            lo = std::lower_bound(v.begin(), v.end(), (uint32_t)first) - v.begin();
+            hi = std::lower_bound(v.begin(), v.end(), (uint32_t)(first + count)) - v.begin();
+        }
+        if (hi > lo) out[n++] = ClassSpan{r->cls_dev[j] + lo, hi - lo, kClsU[j] + k - 1, j == 0};
+    }
+    if (r->preset ? n > 1 : mixed) return n;
+    out[0] = ClassSpan{nullptr, count, std::min<uint32_t>(r->max_len, 512 + k - 1), true};   // a batch of one class is one plain launch
+    return 1;
+}
+
+// Timing events of a launch: [0], [1] around the classify kernels (the tail kernel ahead of them is on the step's account),
+// [2], [3] around what follows them.  Handed to the context by finish_launch, destroyed on any early return.
+struct LaunchEvents {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool timed = false, started = false;
+    ~LaunchEvents() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); }
+    void start(hipStream_t st) {
+        if (timed && !started) hipEventRecord(e[0], st);
+        started = true;
+    }
+};
+
+// One launch of the chain behind the fast classes: a class takes the reads an earlier one listed (`in`, their number in the
+// cursor word in_word; null: the batch itself) and lists those it cannot hold either in `out` (counted in out_word; null: it is the
+// last resort).
+struct Tier {
+    int tcap_class;             // launch_classify's
+    const DevBuf* in;  int in_word;
+    const DevBuf* out; int out_word;
+    uint32_t max_len;           // length bound: picks the U class inside the tier
+    uint32_t p_min, p_max;      // only the listed reads with this many k-mer positions
+    hipStream_t stream;
+    bool on;
+};
+static bool launch_tier(const BatchSet& s, const ClassifyArgs& a, const Tier& t) {
+    ClassifyArgs x = a;
+    if (t.in) { x.index = t.in->as<uint32_t>(); x.count_ptr = s.word(t.in_word); x.count = 0; }
+    x.ovf_list = t.out ? t.out->as<uint32_t>() : nullptr;
+    x.ovf_slot = (uint32_t)t.out_word;
+    x.p_min = t.p_min;
+    x.p_max = t.p_max;
+    return launch_classify(x, t.max_len, t.tcap_class, t.stream);
+}
+
+// The end of every launch: the set's `done` behind its last kernel on the joining stream (launch_k4_end has recorded it there
+// already), the timing events to the context.
+static int finish_launch(lmat_ctx* c, BatchSet& s, LaunchEvents& ev, hipStream_t js, bool done_recorded) {
+    c->join_stream = js;
+    if (!done_recorded) HIPCHK(c, hipEventRecord(s.done, js));
+    s.in_flight = true;
+    if (ev.timed) {
+        HIPCHK(c, hipEventRecord(ev.e[3], js));
+        c->pending_events.push_back(std::make_pair(ev.e[0], ev.e[1]));
+        c->pending_events2.push_back(std::make_pair(ev.e[2], ev.e[3]));
+        ev.e[0] = ev.e[1] = ev.e[2] = ev.e[3] = nullptr;
+    }
+    HIPCHK(c, hipGetLastError());
+    return LMAT_OK;
+}
+
 // pipelined: the launch takes the other set of per-batch buffers and returns with its decision kernels still running on the
 // side streams (beside whatever the caller queues next on the context's stream); the set's `done` event marks their end.
 // Otherwise the context's stream waits for them, as every caller that reads results right away needs.
@@ -1493,264 +1580,115 @@ static int run_classify(lmat_ctx* c, const lmat_reads* reads, uint64_t first, ui
     if (!c->db_ready) return set_err(c, LMAT_E_ARG, "database not ready");
     if (first + count > reads->n) return set_err(c, LMAT_E_ARG, "read range out of bounds");
     if (count > 0xFFFFFFFFull) return set_err(c, LMAT_E_ARG, "batch above 2^32 reads");
-    hipSetDevice(c->device);
-    if (pipelined) swap_sets(c);
-    if (!c->ev_done) HIPCHK(c, hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-    if (c->set_in_flight) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_done, 0));  // the set's previous batch has to be through
-    int rc = ensure_results(c, c->out_results ? 0 : count, want_cands && !c->out_cands ? cand_cap : 0);
-    if (!rc) rc = ensure_scratch(c, count);
-    if (rc) return rc;
     if (reads->n > 0xFFFFFFFFull) return set_err(c, LMAT_E_ARG, "read set above 2^32 reads");
-    if ((int)reads->max_len > classify_max_read_len())
-        return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
-    if (!c->d_gscratch)  // per-read tables of the global-memory class (very long reads, very large taxid tables)
-        HIPCHK(c, hipMalloc((void**)&c->d_gscratch, classify_gmem_scratch_bytes()));
-    // per-launch counters: the candidate cursor [0] and the list lengths [2..]; the error word (d_err) is sticky -- launches
-    // only OR into it and whoever reports it (lmat_sync, lmat_classify, lmat_rand_label) clears it
-    HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, want_cands ? kCursorBytes : (size_t)kCursorWords * 4, c->stream));  // (the sub-cursors start empty: next free = end = 0)
-    ClassifyArgs a = make_args(c, reads, first, count, want_cands, cand_cap);
-    // Tails (tail_kernel): where the reads of the 160-k-mer class end a few positions past their second chunk -- 150 bp reads
-    // at k = 20 have 131 -- those positions are looked up beforehand, 4, 8 or 16 lanes per read.  Compact layout, no null
-    // models (their GC accounting walks every chunk).  LMAT_TAIL=0 turns it off.
-    auto setup_tail = [&](bool single_class) {  // single_class: the whole batch runs in the class its longest read asks for
-        static const bool tail_on = !getenv("LMAT_TAIL") || atoi(getenv("LMAT_TAIL")) != 0;
-        static const int tail_force = getenv("LMAT_TAIL_LPR") ? atoi(getenv("LMAT_TAIL_LPR")) : 0;  // experiments: 4, 8 or 16
-        const uint32_t k = (uint32_t)c->dev.k;
-        const uint32_t realP = reads->max_len >= k ? reads->max_len - k + 1 : 0;
-        if (single_class && realP > 160u) return;
-        const uint32_t maxP = std::min<uint32_t>(realP, 160u);
-        uint32_t lpr = 0;
-        if (tail_on && c->dev.cpt.nb && !c->nm.active && maxP > 128u) lpr = maxP <= 132u ? 4u : (maxP <= 136u ? 8u : 16u);
-        if (lpr && (tail_force == 4 || tail_force == 8 || tail_force == 16) && 128u + (uint32_t)tail_force >= std::min(maxP, 144u)) lpr = (uint32_t)tail_force;
-        if (lpr) {
-            const uint64_t need = count * (16ull * lpr + 32ull);
-            if (need > c->tail_bytes) {
-                if (c->d_tail) hipFree(c->d_tail);
-                c->d_tail = nullptr; c->tail_bytes = 0;
-                if (hipMalloc((void**)&c->d_tail, need) == hipSuccess) c->tail_bytes = need;
-                else { (void)hipGetLastError(); lpr = 0; }  // no room for them: the reads run their third chunk
-            }
-        }
-        if (lpr) {
-            a.tail_lpr = lpr;
-            a.tail16 = (const uint32_t*)c->d_tail;
-            a.tail_u = (const uint64_t*)(c->d_tail + count * 16ull * lpr);
-        }
-    };
-    auto tail_launch = [&](const ClassifyArgs& s) { launch_tail(s, c->stream); };  // (on a stream of its own beside the batch before: measured, no gain -- it takes the same wave slots)
-    struct Ev {  // timing events of this launch: handed to the context on success, destroyed on any early return
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Ev() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); }
-    } ev;
-    hipEvent_t &e0 = ev.e[0], &e1 = ev.e[1], &e2 = ev.e[2], &e3 = ev.e[3];
-    if (timed) {
-        HIPCHK(c, hipEventCreate(&e0));
-        HIPCHK(c, hipEventCreate(&e1));
-        HIPCHK(c, hipEventCreate(&e2));
-        HIPCHK(c, hipEventCreate(&e3));
-    }
-    bool started = false;
-    auto mark_start = [&]() {  // the first timing event brackets the classify kernels only: the tail kernel ahead of them is on the step's account
-        if (timed && !started) hipEventRecord(e0, c->stream);
-        started = true;
-    };
+    if ((int)reads->max_len > classify_max_read_len()) return err_read_too_long(c);
+    if (c->dev.wide && !c->dev.cpt.nb) return set_err(c, LMAT_E_ARG, "a wide taxonomy needs the compact table layout (k >= 10)");
+    hipSetDevice(c->device);
+    int rc = prepare_set(c, count, want_cands, cand_cap, pipelined);
+    if (rc) return rc;
+    BatchSet& s = c->set();
+    ClassifyArgs a = make_args(c, s, reads, first, count, want_cands, cand_cap);
+    LaunchEvents ev;
+    ev.timed = timed;
+    if (timed) for (hipEvent_t& e : ev.e) HIPCHK(c, hipEventCreate(&e));
+    const uint32_t k = (uint32_t)c->dev.k, max_len = reads->max_len, all = 0xFFFFFFFFu;
+    const DevBuf* ovf = s.ovf;
     if (c->dev.wide) {
         // A wide taxonomy (more than 65534 ids): the classes with 32-bit ids in their tables, which decide in-kernel -- a first
         // tier of 128 taxids / 512 list elements (five waves per CU), a second of 512 / 2048, then tables in global memory.  The
         // 16-bit fast classes do not apply; this path is built for correctness on databases of 32-bit taxids, not for the headline.
-        if (!c->dev.cpt.nb) return set_err(c, LMAT_E_ARG, "a wide taxonomy needs the compact table layout (k >= 10)");
-        const uint32_t kk = (uint32_t)c->dev.k;
-        mark_start();
-        ClassifyArgs w = a;
-        w.gscratch = c->d_gscratch;
-        bool ok = true;
-        if (reads->max_len <= 512 + kk - 1) {
-            w.ovf_list = c->d_ovf; w.ovf_slot = 2;
-            ok = launch_classify(w, reads->max_len, 4, c->stream);
-            w.index = c->d_ovf; w.count_ptr = c->d_cursor + 2; w.count = 0;
-        }
-        if (ok && reads->max_len <= 2048 + kk - 1) {
-            w.ovf_list = c->d_ovf2; w.ovf_slot = 3;
-            ok = launch_classify(w, reads->max_len, 5, c->stream);
-            w.index = c->d_ovf2; w.count_ptr = c->d_cursor + 3; w.count = 0;
-        }
-        w.ovf_list = nullptr; w.ovf_slot = 7;
-        if (ok) ok = launch_classify(w, reads->max_len, 1, c->stream);
-        if (!ok) return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
-        if (timed) { HIPCHK(c, hipEventRecord(e1, c->stream)); HIPCHK(c, hipEventRecord(e2, c->stream)); }
-        c->join_stream = c->stream;
-        HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
-        c->set_in_flight = true;
-        if (timed) {
-            HIPCHK(c, hipEventRecord(e3, c->stream));
-            c->pending_events.push_back(std::make_pair(e0, e1));
-            c->pending_events2.push_back(std::make_pair(e2, e3));
-            e0 = e1 = e2 = e3 = nullptr;
-        }
-        HIPCHK(c, hipGetLastError());
-        return LMAT_OK;
+        ev.start(c->stream);
+        a.gscratch = c->gscratch.as<unsigned char>();
+        const bool t1 = max_len <= 512 + k - 1, t2 = max_len <= 2048 + k - 1;   // (reads beyond 531 bp start in the second tier)
+        const Tier chain[] = {
+            {4, nullptr, 0, &ovf[0], kCurOvfFast, max_len, 0, all, c->stream, t1},
+            {5, t1 ? &ovf[0] : nullptr, kCurOvfFast, &ovf[1], kCurOvfE512, max_len, 0, all, c->stream, t2},
+            {1, t2 ? &ovf[1] : nullptr, kCurOvfE512, nullptr, kCurOvfLarge, max_len, 0, all, c->stream, true}};
+        for (const Tier& t : chain)
+            if (t.on && !launch_tier(s, a, t)) return err_read_too_long(c);
+        if (timed) { HIPCHK(c, hipEventRecord(ev.e[1], c->stream)); HIPCHK(c, hipEventRecord(ev.e[2], c->stream)); }
+        return finish_launch(c, s, ev, c->stream, false);
     }
-    // Each read runs in the smallest fast class that holds it (160 / 256 / 512 k-mers; 512 = 531 bp at k = 20); longer
-    // reads ride the overflow list to the wave-per-read classes behind it.  A batch of one class is one plain launch.
-    {
-        lmat_reads* rw = const_cast<lmat_reads*>(reads);
-        const uint32_t k = (uint32_t)c->dev.k;
-        if (!rw->preset && rw->cls_k != (int)k && rw->lens.size() == rw->n) {
-            for (int j = 0; j < kNCls; ++j) { rw->cls_host[j].clear(); if (rw->cls_dev[j]) { hipFree(rw->cls_dev[j]); rw->cls_dev[j] = nullptr; } }
-            for (uint64_t i = 0; i < rw->n; ++i) {
-                const uint32_t P = rw->lens[i] >= k ? rw->lens[i] - k + 1 : 0;
-                rw->cls_host[len_class(P)].push_back((uint32_t)i);
-            }
-            int used = 0;
-            for (int j = 0; j < kNCls; ++j) used += !rw->cls_host[j].empty();
-            if (used > 1)
-                for (int j = 0; j < kNCls; ++j)
-                    if (!rw->cls_host[j].empty()) {
-                        HIPCHK(c, hipMalloc((void**)&rw->cls_dev[j], rw->cls_host[j].size() * 4));
-                        HIPCHK(c, hipMemcpyAsync(rw->cls_dev[j], rw->cls_host[j].data(), rw->cls_host[j].size() * 4, hipMemcpyHostToDevice, c->stream));
-                    }
-            rw->cls_k = (int)k;
-        }
-        const uint32_t cls_len[kNCls] = {kClsU[0] + k - 1, kClsU[1] + k - 1, kClsU[2] + k - 1, kClsU[3] + k - 1};
-        bool mixed = rw->cls_dev[0] || rw->cls_dev[1] || rw->cls_dev[2] || rw->cls_dev[3];
-        if (rw->preset) {  // a stream slot: lists over the whole batch, already on the device
-            const int used = (rw->cls_n[0] != 0) + (rw->cls_n[1] != 0) + (rw->cls_n[2] != 0) + (rw->cls_n[3] != 0);
-            setup_tail(used <= 1);
-            if (used <= 1) {
-                tail_launch(a);
-                mark_start();
-                if (!launch_classify(a, std::min<uint32_t>(reads->max_len, 512 + k - 1), 0, c->stream))
-                    return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
-            } else {
-                for (int j = 0; j < kNCls; ++j) {
-                    if (!rw->cls_n[j]) continue;
-                    ClassifyArgs s = a;
-                    s.index = rw->cls_dev[j];
-                    s.count = rw->cls_n[j];
-                    if (j == 0) tail_launch(s);
-                    mark_start();
-                    if (!launch_classify(s, cls_len[j], 0, c->stream))
-                        return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
-                }
-            }
-        } else if (!mixed) {
-            setup_tail(true);
-            tail_launch(a);
-            mark_start();
-            if (!launch_classify(a, std::min<uint32_t>(reads->max_len, 512 + k - 1), 0, c->stream))
-                return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
-        } else {
-            setup_tail(false);
-            for (int j = 0; j < kNCls; ++j) {
-                const std::vector<uint32_t>& v = rw->cls_host[j];
-                const size_t lo = std::lower_bound(v.begin(), v.end(), (uint32_t)first) - v.begin();
-                const size_t hi = std::lower_bound(v.begin(), v.end(), (uint32_t)(first + count)) - v.begin();
-                if (hi == lo) continue;
-                ClassifyArgs s = a;
-                s.index = rw->cls_dev[j] + lo;
-                s.count = hi - lo;
-                if (j == 0) tail_launch(s);
-                mark_start();
-                if (!launch_classify(s, cls_len[j], 0, c->stream))
-                    return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
-            }
-        }
+    if ((rc = build_class_lists(c, const_cast<lmat_reads*>(reads)))) return rc;
+    ClassSpan spans[kNCls];
+    const int n_spans = class_spans(c, reads, first, count, spans);
+    plan_tail(c, s, reads, n_spans == 1 && !spans[0].index, a);
+    for (int i = 0; i < n_spans; ++i) {
+        ClassifyArgs f = a;
+        f.index = spans[i].index;
+        f.count = spans[i].count;
+        if (spans[i].tail) launch_tail(f, c->stream);  // (on a stream of its own beside the batch before: measured, no gain -- it takes the same wave slots)
+        ev.start(c->stream);
+        if (!launch_classify(f, spans[i].max_len, 0, c->stream)) return err_read_too_long(c);
     }
-    mark_start();  // (no class had a read)
+    ev.start(c->stream);  // (no class had a read)
     if (timed) {
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        HIPCHK(c, hipEventRecord(e2, c->stream));
+        HIPCHK(c, hipEventRecord(ev.e[1], c->stream));
+        HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
     }
-    {   // reads the fast classes could not hold (length, taxids, list elements), listed on the device: first the fast
-        // kernel with room for 512 list elements -- reads over k-mers shared by many strains --, whose own leftovers go on
-        ClassifyArgs m = a;
-        m.index = c->d_ovf;
-        m.count_ptr = c->d_cursor + 2;
-        m.count = 0;
-        m.ovf_list = c->d_ovf2;
-        m.ovf_slot = 3;
-        m.p_max = 160;   // two launches over the one list: reads of up to 160 k-mers in the leaner variant, the rest in the 512 one
-        launch_classify(m, 160 + (uint32_t)c->dev.k - 1, 2, c->stream);
-        m.p_min = 161;
-        m.p_max = 0xFFFFFFFFu;
-        launch_classify(m, 512 + (uint32_t)c->dev.k - 1, 2, c->stream);
-    }
+    // Reads the fast classes could not hold (length, taxids, list elements), listed on the device, go down this chain: first
+    // the fast kernel with room for 512 list elements -- reads over k-mers shared by many strains; two launches over the one
+    // list, reads of up to 160 k-mers in the leaner variant --, then the middle tier (256 taxids, 1024 list elements; four waves
+    // per CU), the large LDS class (1024 taxids, reads up to 2067 bp) and the global-memory class, which a batch with reads
+    // beyond the large class goes to directly.  From the middle tier on the kernels make their own decision step, so they run
+    // beside the K4 kernels.
     const bool k4 = a.prm.stop_after == 0 || a.prm.stop_after >= 10;  // 10..12: partial decision steps (timing experiments)
-    if (k4) {  // score + LCA decision, one lane per read
-        if (!c->stream2) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-        }
-        if (!c->stream3) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_join3, hipEventDisableTiming));
-        }
-        launch_k4_begin(a, c->stream, c->stream2, c->stream3, pipelined ? c->stream3 : c->stream, c->ev_fork);
+    static const bool rerun_side = getenv("LMAT_RERUN_SIDE") && atoi(getenv("LMAT_RERUN_SIDE")) != 0;  // experiments
+    static const bool mid_on = !getenv("LMAT_MID_TIER") || atoi(getenv("LMAT_MID_TIER")) != 0;  // (0: as before this tier existed, for A/B runs)
+    const bool mid_tier = mid_on && max_len <= 512 + k - 1, lds_class = max_len <= 2048 + 19;
+    const int n_e512 = 2;   // the rows that run before the K4 kernels start, without the global-memory scratch
+    if (k4 && !c->stream2) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
-    {   // ... to the large LDS class (1024 taxids, reads up to 2067 bp), or directly to the global-memory class when the
-        // batch holds reads beyond that.  These kernels make their own decision step, so they run beside the K4 kernels.
-        static const bool rerun_side = getenv("LMAT_RERUN_SIDE") && atoi(getenv("LMAT_RERUN_SIDE")) != 0;  // experiments
-        hipStream_t rs = k4 && (pipelined || rerun_side) ? c->stream3 : c->stream;
-        const bool lds_class = reads->max_len <= 2048 + 19;
-        static const bool mid_on = !getenv("LMAT_MID_TIER") || atoi(getenv("LMAT_MID_TIER")) != 0;  // (0: as before this tier existed, for A/B runs)
-        const bool mid_tier = mid_on && reads->max_len <= 512 + (uint32_t)c->dev.k - 1;
-        ClassifyArgs b = a;
-        b.index = c->d_ovf2;
-        b.count_ptr = c->d_cursor + 3;
-        b.count = 0;
-        b.gscratch = c->d_gscratch;
-        if (mid_tier) {  // first the middle tier (256 taxids, 1024 list elements; four waves per CU), whose leftovers go on
-            b.ovf_list = c->d_ovf4;
-            b.ovf_slot = 10;
-            launch_classify(b, reads->max_len, 3, rs);
-            b.index = c->d_ovf4;
-            b.count_ptr = c->d_cursor + 10;
-        }
-        b.ovf_list = lds_class ? c->d_ovf3 : nullptr;  // the global-memory class is the last resort
-        b.ovf_slot = 7;
-        launch_classify(b, reads->max_len, 1, rs);
-        if (lds_class) {  // what even that class cannot hold goes to the global-memory class
-            ClassifyArgs g = b;
-            g.index = c->d_ovf3;
-            g.count_ptr = c->d_cursor + 7;
-            g.ovf_list = nullptr;
-            launch_classify(g, 2048 + 20, 1, rs);
-        }
+    if (k4 && !c->stream3) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_join3, hipEventDisableTiming));
+    }
+    if (k4 && !c->ev_join_small) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join_small, hipEventDisableTiming));
+    hipStream_t rs = k4 && (pipelined || rerun_side) ? c->stream3 : c->stream;
+    const Tier chain[] = {
+        {2, &ovf[0], kCurOvfFast, &ovf[1], kCurOvfE512, 160 + k - 1, 0, 160, c->stream, true},
+        {2, &ovf[0], kCurOvfFast, &ovf[1], kCurOvfE512, 512 + k - 1, 161, all, c->stream, true},
+        {3, &ovf[1], kCurOvfE512, &ovf[2], kCurOvfMid, max_len, 0, all, rs, mid_tier},
+        {1, mid_tier ? &ovf[2] : &ovf[1], mid_tier ? kCurOvfMid : kCurOvfE512, lds_class ? &ovf[3] : nullptr, kCurOvfLarge, max_len, 0, all, rs, true},
+        {1, &ovf[3], kCurOvfLarge, nullptr, kCurOvfLarge, 2048 + 20, 0, all, rs, lds_class}};
+    ClassifyArgs b = a;
+    b.gscratch = c->gscratch.as<unsigned char>();
+    hipStream_t small = pipelined ? c->stream3 : c->stream;   // where the K4 kernel of the small tables runs
+    for (int i = 0; i < (int)(sizeof(chain) / sizeof(chain[0])); ++i) {
+        if (i == n_e512 && k4) launch_k4_begin(a, c->stream, c->stream2, c->stream3, small, c->ev_fork);  // score + LCA decision, one lane per read
+        if (chain[i].on) launch_tier(s, i < n_e512 ? a : b, chain[i]);
     }
     // the tiers join on the context's stream, or, when the next batch is to run beside them, on the second stream
     hipStream_t js = k4 && pipelined ? c->stream2 : c->stream;
-    c->join_stream = js;
-    if (k4) {
-        if (!c->ev_join_small) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join_small, hipEventDisableTiming));
-        launch_k4_end(a, js, c->stream2, c->stream3, pipelined ? c->stream3 : c->stream, c->ev_join, c->ev_join3, c->ev_join_small, c->ev_done);
-    } else HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
-    c->set_in_flight = true;
-    if (timed) {
-        HIPCHK(c, hipEventRecord(e3, js));
-        c->pending_events.push_back(std::make_pair(e0, e1));
-        c->pending_events2.push_back(std::make_pair(e2, e3));
-        e0 = e1 = e2 = e3 = nullptr;
-    }
-    HIPCHK(c, hipGetLastError());
-    return LMAT_OK;
+    if (k4) launch_k4_end(a, js, c->stream2, c->stream3, small, c->ev_join, c->ev_join3, c->ev_join_small, s.done);
+    return finish_launch(c, s, ev, js, k4);
 }
 
-// Reads and clears the sticky error word; maps it to the API's codes (the most specific message wins).
+// Device error flags -> the API's code and message (the most specific message wins); LMAT_OK for none.
+struct DeviceError { int code; const char* msg; };
+static DeviceError device_error(uint32_t flags) {
+    if (!flags) return {LMAT_OK, ""};
+    if (flags & kErrReadTooLong) return {LMAT_E_CAPACITY, "read longer than the kernel's k-mer capacity"};
+    if (flags & kErrLineageTrunc) return {LMAT_E_CAPACITY, "taxonomy deeper than the lineage scratch (72 levels)"};
+    if (flags & kErrNoNullModel) return {LMAT_E_TAXONOMY, "ERROR, ALL TAXIDS MUST HAVE NULL MODELS"};
+    if (flags & kErrTidOverflow) return {LMAT_E_CAPACITY, "a read exceeds the largest tables (4096 taxids / 16384 list elements)"};
+    if (flags & kErrCandOverflow) return {LMAT_E_CAPACITY, "candidate buffer too small (cand_cap)"};
+    return {LMAT_E_DEVICE, "unknown device error flag"};
+}
+
+// Reads and clears the sticky error word; maps it to the API's codes.
 static int report_device_errors(lmat_ctx* c, uint32_t* cand_cursor) {
     uint32_t cur[2];
-    HIPCHK(c, hipMemcpy(&cur[0], c->d_cursor, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&cur[0], c->set().word(kCurCand), 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(&cur[1], c->d_err, 4, hipMemcpyDeviceToHost));
     if (cand_cursor) *cand_cursor = cur[0];
     if (!cur[1]) return LMAT_OK;
     HIPCHK(c, hipMemset(c->d_err, 0, 4));
-    if (cur[1] & kErrReadTooLong) return set_err(c, LMAT_E_CAPACITY, "read longer than the kernel's k-mer capacity");
-    if (cur[1] & kErrLineageTrunc) return set_err(c, LMAT_E_CAPACITY, "taxonomy deeper than the lineage scratch (72 levels)");
-    if (cur[1] & kErrNoNullModel) return set_err(c, LMAT_E_TAXONOMY, "ERROR, ALL TAXIDS MUST HAVE NULL MODELS");
-    if (cur[1] & kErrTidOverflow)
-        return set_err(c, LMAT_E_CAPACITY, "a read exceeds the largest tables (4096 taxids / 16384 list elements)");
-    if (cur[1] & kErrCandOverflow) return set_err(c, LMAT_E_CAPACITY, "candidate buffer too small (cand_cap)");
-    return set_err(c, LMAT_E_DEVICE, "unknown device error flag");
+    const DeviceError e = device_error(cur[1]);
+    return set_err(c, e.code, e.msg);
 }
 
 int lmat_classify(lmat_ctx* c, const lmat_reads* reads, uint64_t first, uint64_t count, lmat_read_result* results,
@@ -1761,21 +1699,23 @@ int lmat_classify(lmat_ctx* c, const lmat_reads* reads, uint64_t first, uint64_t
     hipSetDevice(c->device);
     // a launch that ends in an error (say, cand_cap too small) has still tallied its reads: keep a copy of the tallies
     // so that the caller's retry does not count the batch twice
-    if (c->d_counts && !c->d_counts_bak) HIPCHK(c, hipMalloc(&c->d_counts_bak, c->counts_bytes));
-    if (c->d_counts) HIPCHK(c, hipMemcpyAsync(c->d_counts_bak, c->d_counts, c->counts_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (c->d_counts) {
+        HIPCHK(c, c->counts_bak.ensure(c->counts_bytes));
+        HIPCHK(c, hipMemcpyAsync(c->counts_bak.p, c->d_counts, c->counts_bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
     int rc = run_classify(c, reads, first, count, want, cand_cap, false);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint32_t cand_cursor = 0;
     rc = report_device_errors(c, &cand_cursor);
     if (rc) {
-        if (c->d_counts) HIPCHK(c, hipMemcpy(c->d_counts, c->d_counts_bak, c->counts_bytes, hipMemcpyDeviceToDevice));
+        if (c->d_counts) HIPCHK(c, hipMemcpy(c->d_counts, c->counts_bak.p, c->counts_bytes, hipMemcpyDeviceToDevice));
         return rc;
     }
-    HIPCHK(c, hipMemcpy(results, c->d_results, count * sizeof(lmat_read_result), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(results, c->set().results.p, count * sizeof(lmat_read_result), hipMemcpyDeviceToHost));
     if (want) {
         const uint64_t used = std::min<uint64_t>(cand_cursor, cand_cap);
-        if (used) HIPCHK(c, hipMemcpy(cands, c->d_cands, used * sizeof(lmat_cand), hipMemcpyDeviceToHost));
+        if (used) HIPCHK(c, hipMemcpy(cands, c->set().cands.p, used * sizeof(lmat_cand), hipMemcpyDeviceToHost));
         if (n_cands) *n_cands = used;
     } else if (n_cands) *n_cands = 0;
     return LMAT_OK;
@@ -1797,8 +1737,8 @@ int lmat_sync(lmat_ctx* c, float* kernel_ms_total, uint64_t* kernel_launches) {
     if (!c) return LMAT_E_ARG;
     hipSetDevice(c->device);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->set_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_done)); c->set_in_flight = false; }  // decision kernels on the side streams
-    if (c->parked.in_flight) { HIPCHK(c, hipEventSynchronize(c->parked.done)); c->parked.in_flight = false; }
+    for (auto& s : c->sets)
+        if (s.in_flight) { HIPCHK(c, hipEventSynchronize(s.done)); s.in_flight = false; }  // decision kernels on the side streams
     if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));  // the timing events behind them
     for (auto& e : c->pending_events) {
         float ms = 0;
@@ -1825,11 +1765,11 @@ int lmat_sync(lmat_ctx* c, float* kernel_ms_total, uint64_t* kernel_launches) {
     if (getenv("LMAT_DEBUG")) {
         uint32_t cur[16];
         uint32_t err = 0;
-        HIPCHK(c, hipMemcpy(cur, c->d_cursor, 64, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(cur, c->set().cursor.p, 64, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(&err, c->d_err, 4, hipMemcpyDeviceToHost));
         fprintf(stderr, "[lmat] last launch: cand cursor %u, error flags (all launches since the last report) %u; reads passed on by the fast classes %u, "
                         "by the E=512 class %u, by the middle tier (T=256) %u, by the large LDS class %u; general decision path: small tables %u, large %u\n",
-                cur[0], err, cur[2], cur[3], cur[10], cur[7], cur[4], cur[5]);
+                cur[kCurCand], err, cur[kCurOvfFast], cur[kCurOvfE512], cur[kCurOvfMid], cur[kCurOvfLarge], cur[kCurK4Small], cur[kCurK4Large]);
     }
     return report_device_errors(c, nullptr);  // flags of every launch since the last report, not just the last one
 }
@@ -1879,13 +1819,8 @@ int lmat_rand_label(lmat_ctx* c, const lmat_reads* reads, uint64_t first, uint64
     hipSetDevice(c->device);
     for (uint64_t i = 0; i < count; ++i)
         if (gc_bucket[i] >= c->rand_nb) return set_err(c, LMAT_E_ARG, "GC bucket out of range");
-    if (count > c->rand_gc_cap) {
-        if (c->d_rand_gc) hipFree(c->d_rand_gc);
-        c->d_rand_gc = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->d_rand_gc, count));
-        c->rand_gc_cap = count;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_rand_gc, gc_bucket, count, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->rand_gc.ensure(count));
+    HIPCHK(c, hipMemcpyAsync(c->rand_gc.p, gc_bucket, count, hipMemcpyHostToDevice, c->stream));
     const lmat_params keep = c->params;
     c->params.min_kmer = 1;      // "if (valid_kmers > 0)", rand_read_label.cpp:382
     c->params.min_fnd_kmer = 0;
@@ -1940,41 +1875,53 @@ int lmat_nullmodel_clear(lmat_ctx* c) {
     return LMAT_OK;
 }
 
-// Test hook: the decision kernels' code on candidate tables given from outside (include/lmat_hip.h).
-int lmat_debug_decide(lmat_ctx* c, const uint32_t* tids, const float* scores, const uint64_t* off, const float* stdev, uint64_t n,
-                      lmat_read_result* results) {
-    if (!c || !tids || !scores || !off || !stdev || !results) return LMAT_E_ARG;
+// ---- test hooks of the decision step (include/lmat_hip.h): candidate tables given from outside ----
+// what both entries ask first; the tables' taxids as internal indices (counts, when given, have to fit the 16 bits of a table word)
+static int debug_tables(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, uint64_t total, std::vector<uint32_t>& idx) {
     if (!c->tax.loaded) return set_err(c, LMAT_E_ARG, "load the taxonomy first");
     if (c->tax.wide) return set_err(c, LMAT_E_ARG, "the debug entries of the decision step take taxonomies of up to 65534 ids");
-    if (!n) return LMAT_OK;
-    hipSetDevice(c->device);
-    const uint64_t total = off[n];
-    std::vector<uint32_t> idx(total);
+    idx.resize(total);
     for (uint64_t i = 0; i < total; ++i) {
         auto it = c->tax.index_of.find(tids[i]);
         if (it == c->tax.index_of.end()) return set_err(c, LMAT_E_TAXONOMY, "taxid " + std::to_string(tids[i]) + " is not in the taxonomy");
         idx[i] = it->second;
+        if (counts && counts[i] > 0xFFFFu) return set_err(c, LMAT_E_ARG, "a count above 65535");
     }
-    uint32_t* d_idx = nullptr; float *d_sc = nullptr, *d_sd = nullptr; uint64_t* d_off = nullptr; lmat_read_result* d_res = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_idx, std::max<uint64_t>(total, 1) * 4));
-    HIPCHK(c, hipMalloc((void**)&d_sc, std::max<uint64_t>(total, 1) * 4));
-    HIPCHK(c, hipMalloc((void**)&d_sd, n * 4));
-    HIPCHK(c, hipMalloc((void**)&d_off, (n + 1) * 8));
-    HIPCHK(c, hipMalloc((void**)&d_res, n * sizeof(lmat_read_result)));
-    HIPCHK(c, hipMemcpyAsync(d_idx, idx.data(), total * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scores, total * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sd, stdev, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    return LMAT_OK;
+}
+// a temporary of theirs, filled on the context's stream; it frees itself when the entry returns, early or not
+static int debug_put(lmat_ctx* c, DevBuf& b, const void* src, size_t bytes) {
+    HIPCHK(c, b.ensure(bytes));
+    HIPCHK(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return LMAT_OK;
+}
+static int debug_fetch(lmat_ctx* c, const DevBuf& res, uint64_t n, lmat_read_result* results) {
+    HIPCHK(c, hipMemcpyAsync(results, res.p, n * sizeof(lmat_read_result), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LMAT_OK;
+}
+
+// The decision kernels' code on (taxid, score) tables.
+int lmat_debug_decide(lmat_ctx* c, const uint32_t* tids, const float* scores, const uint64_t* off, const float* stdev, uint64_t n,
+                      lmat_read_result* results) {
+    if (!c || !tids || !scores || !off || !stdev || !results) return LMAT_E_ARG;
+    std::vector<uint32_t> idx;
+    int rc = debug_tables(c, tids, nullptr, n ? off[n] : 0, idx);
+    if (rc || !n) return rc;
+    hipSetDevice(c->device);
+    const uint64_t total = off[n];
+    DevBuf d_idx, d_sc, d_sd, d_off, d_res;
+    if ((rc = debug_put(c, d_idx, idx.data(), total * 4)) || (rc = debug_put(c, d_sc, scores, total * 4)) ||
+        (rc = debug_put(c, d_sd, stdev, n * 4)) || (rc = debug_put(c, d_off, off, (n + 1) * 8))) return rc;
+    HIPCHK(c, d_res.ensure(n * sizeof(lmat_read_result)));
     ClassifyArgs a;
     a.tb = c->dev;
     a.prm = kparams(c->params);
     a.prm.stop_after = 0;
-    a.results = d_res;
+    a.results = d_res.as<lmat_read_result>();
     a.nm = NullModelDev();
-    launch_k4_debug(a, d_idx, d_sc, d_off, d_sd, n, c->stream);
-    HIPCHK(c, hipMemcpyAsync(results, d_res, n * sizeof(lmat_read_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(d_idx); hipFree(d_sc); hipFree(d_sd); hipFree(d_off); hipFree(d_res);
+    launch_k4_debug(a, d_idx.as<uint32_t>(), d_sc.as<float>(), d_off.as<uint64_t>(), d_sd.as<float>(), n, c->stream);
+    if ((rc = debug_fetch(c, d_res, n, results))) return rc;
     for (uint64_t i = 0; i < n; ++i)
         if (results[i].status == 255) return set_err(c, LMAT_E_CAPACITY, "a candidate table outside 1..64 entries, or a lineage beyond the scratch");
     return LMAT_OK;
@@ -1985,58 +1932,43 @@ int lmat_debug_decide(lmat_ctx* c, const uint32_t* tids, const float* scores, co
 int lmat_debug_decide_counts(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand, uint64_t n,
                              int on_the_wave, lmat_read_result* results) {
     if (!c || !tids || !counts || !off || !cand || !results) return LMAT_E_ARG;
-    if (!c->tax.loaded) return set_err(c, LMAT_E_ARG, "load the taxonomy first");
-    if (c->tax.wide) return set_err(c, LMAT_E_ARG, "the debug entries of the decision step take taxonomies of up to 65534 ids");
-    if (!n) return LMAT_OK;
+    std::vector<uint32_t> idx;
+    int rc = debug_tables(c, tids, counts, n ? off[n] : 0, idx);
+    if (rc || !n) return rc;
     hipSetDevice(c->device);
     const uint64_t total = off[n];
-    std::vector<uint32_t> idx(total);
-    for (uint64_t i = 0; i < total; ++i) {
-        auto it = c->tax.index_of.find(tids[i]);
-        if (it == c->tax.index_of.end()) return set_err(c, LMAT_E_TAXONOMY, "taxid " + std::to_string(tids[i]) + " is not in the taxonomy");
-        idx[i] = it->second;
-        if (counts[i] > 0xFFFFu) return set_err(c, LMAT_E_ARG, "a count above 65535");
-    }
-    uint32_t *d_idx = nullptr, *d_cn = nullptr, *d_cd = nullptr; uint64_t* d_off = nullptr; lmat_read_result* d_res = nullptr; void* d_tally = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_idx, std::max<uint64_t>(total, 1) * 4));
-    HIPCHK(c, hipMalloc((void**)&d_cn, std::max<uint64_t>(total, 1) * 4));
-    HIPCHK(c, hipMalloc((void**)&d_cd, n * 4));
-    HIPCHK(c, hipMalloc((void**)&d_off, (n + 1) * 8));
-    HIPCHK(c, hipMalloc((void**)&d_res, n * sizeof(lmat_read_result)));
-    HIPCHK(c, hipMalloc(&d_tally, c->counts_bytes));   // k4_wave tallies its calls: into a buffer nobody reads
-    HIPCHK(c, hipMemsetAsync(d_tally, 0, c->counts_bytes, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_idx, idx.data(), total * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_cn, counts, total * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_cd, cand, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, kCursorWords * 4, c->stream));
+    DevBuf d_idx, d_cn, d_cd, d_off, d_res, d_tally;
+    HIPCHK(c, d_tally.ensure(c->counts_bytes));   // k4_wave tallies its calls: into a buffer nobody reads
+    HIPCHK(c, hipMemsetAsync(d_tally.p, 0, c->counts_bytes, c->stream));
+    if ((rc = debug_put(c, d_idx, idx.data(), total * 4)) || (rc = debug_put(c, d_cn, counts, total * 4)) ||
+        (rc = debug_put(c, d_cd, cand, n * 4)) || (rc = debug_put(c, d_off, off, (n + 1) * 8))) return rc;
+    HIPCHK(c, d_res.ensure(n * sizeof(lmat_read_result)));
+    const lmat_ctx::BatchSet& s = c->set();
+    HIPCHK(c, hipMemsetAsync(s.cursor.p, 0, kCursorWords * 4, c->stream));
     ClassifyArgs a;
     a.tb = c->dev;
     a.prm = kparams(c->params);
     a.prm.stop_after = 0;
-    a.results = d_res;
+    a.results = d_res.as<lmat_read_result>();
     a.cands = nullptr;
     a.cand_cap = 0;
-    a.cursor = c->d_cursor;
+    a.cursor = s.word(0);
     a.err = c->d_err;
-    a.counts = d_tally;
+    a.counts = d_tally.p;
     auto it = c->tax.index_of.find(32630);
     a.phix_call_idx = it == c->tax.index_of.end() ? 0 : it->second;
     a.nm = NullModelDev();
-    launch_k4_debug_counts(a, d_idx, d_cn, d_off, d_cd, n, on_the_wave != 0, c->stream);
-    HIPCHK(c, hipMemcpyAsync(results, d_res, n * sizeof(lmat_read_result), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(d_idx); hipFree(d_cn); hipFree(d_cd); hipFree(d_off); hipFree(d_res); hipFree(d_tally);
-    return LMAT_OK;
+    launch_k4_debug_counts(a, d_idx.as<uint32_t>(), d_cn.as<uint32_t>(), d_off.as<uint64_t>(), d_cd.as<uint32_t>(), n, on_the_wave != 0, c->stream);
+    return debug_fetch(c, d_res, n, results);
 }
 
-// Measurement hook: the per-launch counter block of the most recent launch (after lmat_sync): [0] candidate cursor, [2] reads the
-// fast classes passed on, [3] reads the E = 512 class passed on, [10] the middle tier, [7] the large LDS class, [4] / [5] / [8] / [9]
-// reads handed to the general decision path by table size.
+// Measurement hook: the per-launch counter block of the most recent launch (after lmat_sync), words as kernels.hpp's CursorWord
+// names them: [0] candidate cursor, [2] reads the fast classes passed on, [3] reads the E = 512 class passed on, [10] the middle
+// tier, [7] the large LDS class, [4] / [5] / [8] / [9] reads handed to the general decision path by table size.
 int lmat_debug_last_counters(lmat_ctx* c, uint32_t* out16) {
     if (!c || !out16) return LMAT_E_ARG;
     hipSetDevice(c->device);
-    HIPCHK(c, hipMemcpy(out16, c->d_cursor, kCursorWords * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out16, c->set().cursor.p, kCursorWords * 4, hipMemcpyDeviceToHost));
     return LMAT_OK;
 }
 
@@ -2057,9 +1989,9 @@ int lmat_last_timing(const lmat_ctx* c, float* classify_ms, float* decide_ms, ui
 }
 
 int lmat_results_fetch(lmat_ctx* c, uint64_t first, uint64_t count, lmat_read_result* results) {
-    if (!c || !results || first + count > c->results_cap) return LMAT_E_ARG;
+    if (!c || !results || (first + count) * sizeof(lmat_read_result) > c->set().results.bytes) return LMAT_E_ARG;
     hipSetDevice(c->device);
-    HIPCHK(c, hipMemcpy(results, c->d_results + first, count * sizeof(lmat_read_result), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(results, c->set().results.as<lmat_read_result>() + first, count * sizeof(lmat_read_result), hipMemcpyDeviceToHost));
     return LMAT_OK;
 }
 
@@ -2219,7 +2151,8 @@ int lmat_stream_create(lmat_ctx* c, uint64_t max_reads, uint64_t max_bases, uint
                  hipMalloc((void**)&sl.d_cands, sl.cand_cap * sizeof(lmat_cand)) == hipSuccess;
         sl.reads.preset = true;
     }
-    if (ok) ok = ensure_scratch(c, max_reads) == LMAT_OK;
+    for (auto& s : c->sets)   // both sets: pipelined launches take them in turn
+        if (ok) ok = ensure_scratch(c, s, max_reads) == LMAT_OK;
     if (!ok) { stream_free(st); return set_err(c, LMAT_E_NOMEM, "out of (pinned or device) memory for the batch ring"); }
     *out = st;
     return LMAT_OK;
@@ -2253,9 +2186,10 @@ static int stream_launch(lmat_stream* st, lmat_stream::Slot& sl, bool to_scratch
     // streams onto 4 hardware queues, and a copy that shares its queue with the compute stream holds up the next batch's
     // kernels behind it.
     hipStream_t js = c->join_stream;
-    HIPCHK(c, hipMemcpyAsync(sl.h_cursor, c->d_cursor, 4, hipMemcpyDeviceToHost, js));
-    HIPCHK(c, hipMemcpyAsync(sl.h_cursor + 1, c->d_cursor + 15, 4, hipMemcpyDeviceToHost, js));  // this batch's own error flags
-    HIPCHK(c, hipEventRecord(c->ev_done, js));
+    lmat_ctx::BatchSet& s = c->set();
+    HIPCHK(c, hipMemcpyAsync(sl.h_cursor, s.word(kCurCand), 4, hipMemcpyDeviceToHost, js));
+    HIPCHK(c, hipMemcpyAsync(sl.h_cursor + 1, s.word(kCurBatchErr), 4, hipMemcpyDeviceToHost, js));  // this batch's own error flags
+    HIPCHK(c, hipEventRecord(s.done, js));
     HIPCHK(c, hipEventRecord(sl.ev_done, js));
     if (st->s_d2h != js) HIPCHK(c, hipStreamWaitEvent(st->s_d2h, sl.ev_done, 0));
     HIPCHK(c, hipMemcpyAsync(sl.h_results, sl.d_results, sl.n * sizeof(lmat_read_result), hipMemcpyDeviceToHost, st->s_d2h));
@@ -2345,12 +2279,11 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
     sl.reads.n = n;
     sl.reads.n_words = sl.h_rec_off[n];
     sl.reads.max_len = max_len;
-    sl.reads.class_len = max_len;
     const int used = (cn[0] != 0) + (cn[1] != 0) + (cn[2] != 0) + (cn[3] != 0);
     for (int j = 0; j < kNCls; ++j) sl.reads.cls_n[j] = used > 1 ? cn[j] : 0;
     if ((int)max_len > classify_max_read_len()) {  // refused before anything is queued: the slot goes back untouched
         sl.state = 0;
-        return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
+        return err_read_too_long(c);
     }
     if (n) {
         HIPCHK(c, hipMemcpyAsync(sl.d_bases, ext_bases ? ext_bases : sl.h_bases, sl.h_off[n], hipMemcpyHostToDevice, st->s_h2d));
@@ -2409,10 +2342,8 @@ int lmat_stream_next(lmat_stream* st, const lmat_read_result** results, const lm
             const uint32_t fresh = sl.h_cursor[1];
             nc = sl.h_cursor[0];
             if (!(fresh & kErrCandOverflow)) {
-                if (fresh & kErrReadTooLong) return set_err(c, LMAT_E_CAPACITY, "read longer than the kernel's k-mer capacity");
-                if (fresh & kErrLineageTrunc) return set_err(c, LMAT_E_CAPACITY, "taxonomy deeper than the lineage scratch (72 levels)");
-                if (fresh & kErrNoNullModel) return set_err(c, LMAT_E_TAXONOMY, "ERROR, ALL TAXIDS MUST HAVE NULL MODELS");
-                if (fresh & kErrTidOverflow) return set_err(c, LMAT_E_CAPACITY, "a read exceeds the largest tables (4096 taxids / 16384 list elements)");
+                const DeviceError e = device_error(fresh);
+                if (e.code) return set_err(c, e.code, e.msg);
                 break;
             }
             // the batch printed more candidates than the slot holds: grow this slot fourfold and run it again (its packed reads

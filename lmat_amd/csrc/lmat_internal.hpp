@@ -9,6 +9,7 @@
 #include "../../include/lmat_hip.h"
 #include "lmat_common.hpp"
 #include "dbbuild.hpp"
+#include "devbuf.hpp"
 
 namespace lmat {
 
@@ -122,7 +123,6 @@ struct lmat_reads {
     uint64_t n = 0;
     uint64_t n_words = 0;
     uint32_t max_len = 0;
-    uint32_t class_len = 0;       // length that all but the longest 1 % of the reads stay under
     // Length classes of the fast kernel (k-mer capacities 160 / 256 / 320 / 512: lmat::kNCls, lmat::len_class): read indices per class, ascending, so a
     // mixed-length batch runs each read in the smallest class that holds it.  Built on first use for the database's k.
     std::vector<uint32_t> lens;
@@ -161,8 +161,7 @@ struct lmat_ctx {
     int gene_mode = 0;                                   // gene database (gene_label): lists of 32-bit gene ids, no taxonomy involved
     uint32_t* d_rand_max = nullptr;                      // rand_read_label tables [n_ids][rand_nb]
     uint32_t* d_rand_cnt = nullptr;
-    uint8_t* d_rand_gc = nullptr;
-    uint64_t rand_gc_cap = 0;
+    lmat_dev::DevBuf rand_gc;                            // GC bucket of every read of the launch
     uint32_t rand_nb = 0;
     bool rand_launch = false;
     // synthetic generator state
@@ -174,55 +173,42 @@ struct lmat_ctx {
     std::vector<uint16_t> synth_strain_idx;   // [species*S + s] internal index
     std::vector<uint16_t> synth_species_idx;  // [species]
     uint16_t* d_synth_strain_idx = nullptr;
-    // results / tallies on device
-    lmat_read_result* d_results = nullptr;
-    uint64_t results_cap = 0;
-    lmat_cand* d_cands = nullptr;
-    uint64_t cands_cap = 0;
-    uint32_t* d_cursor = nullptr;  // [0] cand cursor, [1] error flags, [2] overflow-list length
-    uint32_t* d_ovf = nullptr;     // reads to re-run with the large-capacity kernel
-    uint32_t* d_k4buf = nullptr;   // records handed from the fast classify kernel to the K4 kernels
-    uint32_t* d_ovf2 = nullptr;    // second overflow list: reads beyond the E=512 class
-    uint32_t* d_ovf3 = nullptr;    // third: reads beyond the large LDS class
-    uint32_t* d_ovf4 = nullptr;    // reads beyond the middle tier (T = 256): the large LDS class takes them
-    unsigned char* d_gscratch = nullptr;  // tables of the global-memory class, allocated on first use
-    uint32_t* d_k4small = nullptr; // index lists of the reads awaiting K4 (k4_compact_kernel)
-    uint32_t* d_k4large = nullptr;
-    uint32_t* d_k4bail = nullptr;
-    unsigned char* d_tail = nullptr;  // tail entries of the batch's reads (tail_kernel): [reads][lpr] x 16 B, then [reads][4] x 8 B
-    uint64_t tail_bytes = 0;
+    // Everything a batch's kernels write besides the tallies: result records, candidates, the counter block (kernels.hpp: CursorWord),
+    // the lists that hand reads from one class to the next, the records and lists of the general decision path, the tail entries.
+    // The buffers grow with the largest batch so far and free themselves.
+    struct BatchSet {
+        lmat_dev::DevBuf results, cands;       // lmat_read_result[], lmat_cand[]: the context's own output (unless out_results / out_cands are set)
+        lmat_dev::DevBuf cursor;               // kCursorBytes: the counter block and the candidate sub-cursors behind it
+        lmat_dev::DevBuf ovf[4];               // [reads] u32 each: reads passed on by the fast classes | the E = 512 class | the middle tier | the large LDS class
+        lmat_dev::DevBuf k4buf;                // [reads][kK4RecWords]: records handed from the fast classify kernel to the K4 kernels
+        lmat_dev::DevBuf k4small, k4large, k4bail;  // [reads] u32, k4large three times that (large tables | up to 32 taxids | up to 16, by rows): k4_compact_kernel's lists
+        lmat_dev::DevBuf tail;                 // tail entries of the batch's reads (tail_kernel): [reads][lpr] x 16 B, then [reads][4] x 8 B
+        uint64_t scratch_reads = 0;            // batch size ovf .. k4bail are allocated for (0 after a failed allocation: the next launch sizes them again)
+        hipEvent_t done = nullptr;             // recorded behind the last kernel that touches the set
+        bool in_flight = false;
+        uint32_t* word(int w) const { return cursor.as<uint32_t>() + w; }
+        ~BatchSet() { if (done) hipEventDestroy(done); }
+    };
+    // Two of them, taken in turn by pipelined launches: the decision kernels of one batch run beside the classify kernel of the next.
+    BatchSet sets[2];
+    int cur_set = 0;
+    BatchSet& set() { return sets[cur_set]; }   // the set of the most recent launch
+    lmat_dev::DevBuf gscratch;     // tables of the global-memory class, allocated on first use
     hipStream_t stream2 = nullptr;  // the scratch K4 kernel runs beside the LDS one
     hipStream_t stream3 = nullptr;  // ... and the LDS kernel of the largest tables beside both
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr, ev_join_small = nullptr;
     uint32_t* d_err = nullptr;      // sticky error flags of every launch since the last report
-    // Two sets of everything a batch's kernels write besides the tallies (result records, candidates, hand-off records,
-    // lists, counters): the decision kernels of one batch run beside the classify kernel of the next.  The members above
-    // (d_results ... d_k4bail, d_cursor) are the set in use; the other one is parked here.
-    struct BatchSet {
-        lmat_read_result* d_results = nullptr; uint64_t results_cap = 0;
-        lmat_cand* d_cands = nullptr; uint64_t cands_cap = 0;
-        uint32_t *d_cursor = nullptr, *d_ovf = nullptr, *d_ovf2 = nullptr, *d_ovf3 = nullptr, *d_ovf4 = nullptr, *d_k4buf = nullptr, *d_k4small = nullptr,
-                 *d_k4large = nullptr, *d_k4bail = nullptr;
-        uint64_t ovf_cap = 0;
-        unsigned char* d_tail = nullptr; uint64_t tail_bytes = 0;
-        hipEvent_t done = nullptr;   // recorded behind the last kernel that touches the set
-        bool in_flight = false;
-    } parked;
-    hipEvent_t ev_done = nullptr;    // `done` of the set in use
-    hipStream_t join_stream = nullptr;  // where the last launch's kernels joined (its `done` was recorded there)
-    bool set_in_flight = false;
+    hipStream_t join_stream = nullptr;  // where the last launch's kernels joined (its set's `done` was recorded there)
     lmat::NullModelDev nm;         // device pointers owned by the context
     std::vector<void*> nm_allocs;
-    uint64_t ovf_cap = 0;
     void* d_counts = nullptr;      // u64 count[n_ids] | f64 score[n_ids] | u64 nomatch[3]
-    void* d_counts_bak = nullptr;  // tallies as they were before the current blocking launch (restored when it fails)
+    lmat_dev::DevBuf counts_bak;   // tallies as they were before the current blocking launch (restored when it fails)
     // where the next launch writes instead of the context's own buffers (set by the streamed boundary around its launches)
     lmat_read_result* out_results = nullptr;
     lmat_cand* out_cands = nullptr;
     void* out_counts = nullptr;
-    bool batch_err = false;        // the next launch keeps its error flags in its own counter block (word 15) instead of the sticky word
+    bool batch_err = false;        // the next launch keeps its error flags in its own counter block (kCurBatchErr) instead of the sticky word
     uint64_t counts_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events;   // around the classify kernel
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events2;  // around the K4 kernels + the larger-class re-runs
     float kernel_ms_total = 0, kernel2_ms_total = 0, last_classify_ms = 0, last_decide_ms = 0;

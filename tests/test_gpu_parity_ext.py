@@ -216,6 +216,48 @@ def test_async_and_calls_only_agree_with_full_output(config1):
     eng.close()
 
 
+def _same_records(got, want):
+    for f in ("status", "match_type", "cand_kmer_cnt", "valid_kmers", "call_tid", "bin_sel"):
+        assert (got[f] == want[f]).all(), f
+    for f in ("call_score", "stdev"):
+        assert (got[f].view(np.uint32) == want[f].view(np.uint32)).all(), f
+
+
+def test_async_slices_regrow_both_batch_sets(small_dataset):
+    """Queued launches over slices of growing size: the two sets of per-batch buffers are taken in turn, so every launch regrows
+    the set it takes (16 -> 112 and 48 -> 224 reads) while the launch before it is still in flight on the other one; a last
+    small launch reuses a set as it is.  Tallies and records equal those of one blocking launch over the 400 reads (mixed
+    lengths, some below k).  The name matches the child run of test_batches_on_one_stream_give_the_same_answers, which repeats
+    this with LMAT_PIPELINE=0: one set, regrown by every launch."""
+    from lmat_amd import Params
+    ds = small_dataset
+    reads = ds["reads"]
+    assert len(reads) == 400
+    ref = _engine(ds)
+    dr = ref.upload_reads(reads)
+    ref.counts_reset()
+    res0, _ = ref.classify(dr)
+    tallies0 = ref.counts()
+    dr.free()
+    ref.close()
+    eng = _engine(ds, Params.run_rl(prn_all=0))   # a fresh engine: both sets start empty
+    dr = eng.upload_reads(reads)
+    eng.counts_reset()
+    lo = 0
+    for n in (16, 48, 112, 224):
+        eng.classify_async(dr, lo, n)
+        lo += n
+    assert lo == len(reads)
+    eng.sync()
+    assert eng.counts() == tallies0
+    _same_records(eng.fetch_results(0, 224), res0[176:400])
+    eng.classify_async(dr, 0, 16)
+    eng.sync()
+    _same_records(eng.fetch_results(0, 16), res0[0:16])
+    dr.free()
+    eng.close()
+
+
 @pytest.mark.parametrize("gb,n_reads,lens", [(8, 1_000_000, (150,)), (64, 2_000_000, (150,)),
                                              (186, 2_000_000, (75, 100, 125, 150, 200, 250, 300))],
                          ids=["config2-8GiB", "config3-64GiB", "config5-shard-186GiB-mixed"])
