@@ -47,6 +47,14 @@ def _compare(eng, orc, reads, first_index=0, cand_per_read=256):
     return res, tally, nm
 
 
+def _assert_tallies(eng, tally, nm):
+    """eng.counts() since the last counts_reset() against the oracle's tally and no-match counters of the same reads: every read
+    counted exactly once, whichever class ended up with it."""
+    counts, nomatch = eng.counts()
+    assert nomatch == nm
+    assert {t: c for t, (c, s) in counts.items()} == {t: c for t, (c, s) in tally.items()}
+
+
 def test_gpu_lookup_matches_reference_sorteddb():
     """The GPU hash returns, for every golden k-mer, what the REFERENCE's SortedDb + TaxNodeStat returned."""
     ds = {k: os.path.join(DS, v) for k, v in dict(tree="tax.dat", depth="depth.dat", rank="rank.txt",
@@ -151,8 +159,12 @@ def test_taxid_table_overflow_rerun(tmp_path):
     synth.write_taxhisto(p["db"], kmers, lists, 20)
     eng = _engine(p)
     orc = _oracle(p)
-    res, _, _ = _compare(eng, orc, [r for _, r in reads], cand_per_read=2048)
+    eng.counts_reset()
+    res, tally, nm = _compare(eng, orc, [r for _, r in reads], cand_per_read=2048)
+    flow = eng.last_counters()
+    _assert_tallies(eng, tally, nm)
     assert res["n_cand"].max() > 128
+    assert flow["past_fast"] >= 1 and flow["past_e512"] >= 1 and flow["past_large"] == 0, flow   # re-run, and by an LDS class
     eng.close()
     orc.close()
     # > 1024 kept taxids: beyond the large LDS class; the global-memory class (4096 taxids) takes the read
@@ -160,8 +172,12 @@ def test_taxid_table_overflow_rerun(tmp_path):
     synth.write_taxhisto(p["db"], kmers, lists, 20)
     eng = _engine(p)
     orc = _oracle(p)
-    res, _, _ = _compare(eng, orc, [r for _, r in reads], cand_per_read=4096)
+    eng.counts_reset()
+    res, tally, nm = _compare(eng, orc, [r for _, r in reads], cand_per_read=4096)
+    flow = eng.last_counters()
+    _assert_tallies(eng, tally, nm)
     assert res["n_cand"].max() > 1024
+    assert flow["past_fast"] >= 2 and flow["past_large"] >= 1, flow   # the second read went all the way to the global-memory class
     eng.close()
     orc.close()
 
@@ -191,7 +207,11 @@ def test_many_distinct_lists_in_one_read(tmp_path):
     synth.write_taxhisto(p["db"], kmers, lists, 20)
     eng = _engine(p)
     orc = _oracle(p)
-    _compare(eng, orc, [r for _, r in reads], cand_per_read=2048)
+    eng.counts_reset()
+    _, tally, nm = _compare(eng, orc, [r for _, r in reads], cand_per_read=2048)
+    flow = eng.last_counters()
+    _assert_tallies(eng, tally, nm)
+    assert flow["past_fast"] >= 2 and flow["past_e512"] >= 2, flow   # both reads left the fast kernel (its E = 512 form has 64 lists too)
     eng.close()
     orc.close()
 
@@ -1170,8 +1190,10 @@ def test_heavy_tail_lists_parity(tmp_path):
             eng.set_label_modes(False, prune, rank_fn)
         eng.synth_db(Glen, k=20, seed=2002, table_bytes=table_bytes, conserved_permille=(20, 10, 5))
         reads = eng.synth_reads(n, lens, seed=seed)
+        eng.counts_reset()
         res, cands = eng.classify(reads, cand_cap=1300 * n)
         flow = eng.last_counters()
+        tallies = eng.counts()
         blob, off = reads.ascii(0, n)
         orc = oracle_py.Oracle(p["tree"], p["depth"], p["rank"], p["idmap"])
         orc.set_k(20)
@@ -1223,9 +1245,10 @@ def test_heavy_tail_lists_parity(tmp_path):
             assert flow["past_fast"] > 0.02 * n and flow["past_e512"] > 0.02 * n and flow["past_middle"] > 0.008 * n and flow["past_large"] > 0.002 * n, flow
         else:
             assert flow["past_e512"] <= 2, flow   # pruned lists: nobody needs more than the fast tiers
-        want, _, _ = orc.classify(np.append(blob, np.uint8(0)), off, 20)
+        want, tally, nm = orc.classify(np.append(blob, np.uint8(0)), off, 20)
         got = eng.format_out(res, cands, (np.append(blob, np.uint8(0)), off))
         assert got == want
+        assert tallies[1] == nm and {t: c for t, (c, s) in tallies[0].items()} == {t: c for t, (c, s) in tally.items()}   # every read once, in whichever tier
         orc.close()
         reads.free()
         eng.close()
