@@ -27,6 +27,8 @@ extern "C" {
 #define LMAT_E_CAPACITY (-4)  /* a fixed on-device capacity was exceeded (message says which) */
 #define LMAT_E_TAXONOMY (-5)  /* inconsistent taxonomy inputs */
 #define LMAT_E_NOMEM (-6)
+#define LMAT_E_STATE (-7)     /* the object is not in the state the call needs (lmat_export_*) */
+#define LMAT_E_INTERNAL (-8)  /* the engine found its own data inconsistent (message says what) */
 
 typedef struct lmat_ctx lmat_ctx;
 typedef struct lmat_reads lmat_reads;
@@ -433,6 +435,40 @@ int lmat_build_merge_stats(const lmat_build* b, lmat_merge_stats* out);   /* aft
  * on the device.  *n is the number of such taxids, set even when cap is too small (LMAT_E_CAPACITY): a cap of 0 asks for it. */
 int lmat_build_taxid_counts(lmat_build* b, uint32_t* tids, uint64_t* counts, uint64_t cap, uint64_t* n);
 
+/* ---- a loaded database back out as tax_histo records ----
+ * The way out of the k-mer table: every k-mer the finalized database of ctx holds, ascending, each with its taxid list AS STORED
+ * (the order and the 32-bit ids of the tax_histo record it came from, whatever label modes shaped the list records) -- from a table
+ * built from files, from either image format, from genomes or from a merge.  What make_db_table's options did to the content
+ * (pruned lists, human / adaptor k-mers) is part of the database and therefore of the export.
+ *   lmat_export_set_options  device_budget_bytes 0: half of the free device memory; prefix_bits -1: the smallest split of the k-mer
+ *                            space (by the top bits of the k-mer) whose pass fits the budget, else 0 .. min(2k, 24)
+ *   lmat_export_run          taxhisto_fn: the file lmat_db_add_taxhisto reads (header count = lmat_db_size), streamed pass by pass;
+ *                            NULL: the records stay in host memory for lmat_export_fetch; "": they are dropped (counts only).  Always the per-taxid counts
+ *                            (frequency_counter, src/frequency_counter.cpp:86-144) are kept for lmat_export_taxid_counts.
+ *   lmat_export_fetch        as lmat_build_fetch;  lmat_export_taxid_counts  as lmat_build_taxid_counts (lists that hold the taxid)
+ *   errors   no finalized database, a fetch before a run or after a run to a file: LMAT_E_STATE.  A synthetic database
+ *            (lmat_synth_db_build*): LMAT_E_STATE.  A pass that does not fit the budget under a forced prefix_bits, or under the
+ *            finest split: LMAT_E_CAPACITY.  The table holds a k-mer twice, or the records written differ from lmat_db_size:
+ *            LMAT_E_INTERNAL.  A failed run leaves no file behind. */
+typedef struct lmat_export lmat_export;
+typedef struct {
+    uint64_t records, entries, singletons;   /* records written, their list entries (Total-tid), lists of one entry */
+    uint64_t from_buckets, from_overflow;    /* records read from the compact buckets | from 8 x u64 slot buckets (overflow table, wide layout) */
+    uint64_t passes;
+    int prefix_bits;
+    double ms_scan, ms_sort, ms_lists, ms_fetch, ms_write;   /* HIP-event time of the device stages; host time of the fetch and the file */
+} lmat_export_stats;
+int lmat_export_create(lmat_ctx* ctx, lmat_export** out);          /* ctx holds a finalized database */
+void lmat_export_destroy(lmat_export* e);
+const char* lmat_export_error(const lmat_export* e);
+int lmat_export_set_options(lmat_export* e, uint64_t device_budget_bytes, int prefix_bits /* -1: derive */);
+int lmat_export_run(lmat_export* e, const char* taxhisto_fn /* NULL: keep the result in host memory */, lmat_export_stats* out);
+int lmat_export_fetch(lmat_export* e, uint64_t first, uint64_t count, uint64_t* kmers, uint64_t* list_off, uint32_t* tids, uint64_t tid_cap);
+int lmat_export_taxid_counts(lmat_export* e, uint32_t* tids, uint64_t* counts, uint64_t cap, uint64_t* n);
+/* A loaded database as one more input of a merge (beside lmat_build_add_taxhisto): src is exported into host memory at the time of
+ * the call and its records take the path a parsed file takes.  k must match (LMAT_E_ARG); a gene database is LMAT_E_ARG. */
+int lmat_build_add_db(lmat_build* b, lmat_ctx* src);
+
 /* ---- per-group k-mer coverage of a set of reads (content_summ's counting, src/content_summ.cpp:113-152, 538-571) ----
  * Input: reads (ASCII, any length, 0 included) with a caller-chosen 32-bit group id each -- content_summ uses the taxid it counts
  * the read under -- and a list of k sizes in 1..31 (duplicates allowed, reported per index).
@@ -497,6 +533,8 @@ int lmat_gather_bench(lmat_ctx* ctx, uint64_t n_probes, uint64_t seed, float* ms
  * minimum).  (bucket, tag) <-> canonical k-mer is a bijection; tests check exactly that.  Needs no device.
  * LMAT_E_ARG when this k has no compact layout (k < 10). */
 int lmat_table_address(int k, uint64_t want_buckets, uint64_t kmer, uint64_t* n_buckets, uint32_t* bucket, uint32_t* tag);
+/* The way back: the canonical k-mer filed under (bucket, tag) in that table.  LMAT_E_ARG for a bucket or tag the geometry has not. */
+int lmat_table_unaddress(int k, uint64_t want_buckets, uint32_t bucket, uint32_t tag, uint64_t* kmer);
 
 /* ---- record text -------------------------------------------------------------
  * The bytes read_label writes to a .out file for these results (prefix

@@ -58,6 +58,16 @@ class CovStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ExportStats(C.Structure):
+    """lmat_export_stats: what lmat_export_run counted, the HIP-event time of the device stages and the host time of fetch and file."""
+    _fields_ = [("records", C.c_uint64), ("entries", C.c_uint64), ("singletons", C.c_uint64), ("from_buckets", C.c_uint64),
+                ("from_overflow", C.c_uint64), ("passes", C.c_uint64), ("prefix_bits", C.c_int), ("ms_scan", C.c_double),
+                ("ms_sort", C.c_double), ("ms_lists", C.c_double), ("ms_fetch", C.c_double), ("ms_write", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 READ_RESULT_DTYPE = np.dtype([("status", "u1"), ("match_type", "u1"), ("cand_kmer_cnt", "<u2"), ("valid_kmers", "<i4"),
                               ("read_len", "<i4"), ("log_avg", "<f4"), ("stdev", "<f4"), ("call_tid", "<u4"),
                               ("call_score", "<f4"), ("cand_off", "<u4"), ("n_cand", "<u4"), ("bin_sel", "<i4")])
@@ -186,6 +196,15 @@ def load_library(path: str | None = None):
         "lmat_cov_run": (i32, [vp, P(CovStats)]),
         "lmat_cov_summary": (i32, [vp, i32, vp, vp, vp, u64, P(u64)]),
         "lmat_cov_histogram": (i32, [vp, i32, u32, vp, vp, u64, P(u64)]),
+        "lmat_export_create": (i32, [vp, P(vp)]),
+        "lmat_export_destroy": (None, [vp]),
+        "lmat_export_error": (cp, [vp]),
+        "lmat_export_set_options": (i32, [vp, u64, i32]),
+        "lmat_export_run": (i32, [vp, cp, P(ExportStats)]),
+        "lmat_export_fetch": (i32, [vp, u64, u64, vp, vp, vp, u64]),
+        "lmat_export_taxid_counts": (i32, [vp, vp, vp, u64, P(u64)]),
+        "lmat_build_add_db": (i32, [vp, vp]),
+        "lmat_table_unaddress": (i32, [i32, u64, u32, u32, P(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -213,7 +232,9 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_build_run", "lmat_build_write_taxhisto", "lmat_build_fetch", "lmat_db_build_from_genomes",
             "lmat_build_add_taxhisto", "lmat_build_merge_stats", "lmat_build_taxid_counts",
             "lmat_cov_create", "lmat_cov_destroy", "lmat_cov_error", "lmat_cov_set_options", "lmat_cov_add_reads", "lmat_cov_run",
-            "lmat_cov_summary", "lmat_cov_histogram"]
+            "lmat_cov_summary", "lmat_cov_histogram",
+            "lmat_export_create", "lmat_export_destroy", "lmat_export_error", "lmat_export_set_options", "lmat_export_run", "lmat_export_fetch",
+            "lmat_export_taxid_counts", "lmat_build_add_db", "lmat_table_unaddress"]
 
 
 def _ptr(a):
@@ -398,6 +419,10 @@ class Builder:
         """An existing tax_histo file as a further input: run() gives the merge (lmat_build_add_taxhisto)."""
         self._chk(self.lib.lmat_build_add_taxhisto(self.h, fn.encode()))
 
+    def add_db(self, engine):
+        """The database `engine` holds as a further input: exported on the GPU now, merged like a file (lmat_build_add_db)."""
+        self._chk(self.lib.lmat_build_add_db(self.h, engine.ctx))
+
     def run(self):
         st = BuildStats()
         self._chk(self.lib.lmat_build_run(self.h, C.byref(st)))
@@ -438,6 +463,56 @@ class Builder:
     def close(self):
         if self.h:
             self.lib.lmat_build_destroy(self.h)
+            self.h = None
+
+
+class Export:
+    """lmat_export: the finalized database of `eng` back out as tax_histo records, on its GPU."""
+
+    def __init__(self, eng):
+        self.eng, self.lib = eng, eng.lib
+        h = C.c_void_p()
+        eng._chk(self.lib.lmat_export_create(eng.ctx, C.byref(h)))
+        self.h = h
+        self.stats = None
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise LmatError(rc, self.lib.lmat_export_error(self.h).decode(errors="replace"))
+
+    def set_options(self, budget_bytes=0, prefix_bits=-1):
+        self._chk(self.lib.lmat_export_set_options(self.h, int(budget_bytes), int(prefix_bits)))
+
+    def run(self, out=None):
+        st = ExportStats()
+        self._chk(self.lib.lmat_export_run(self.h, out.encode() if out is not None else None, C.byref(st)))
+        self.stats = st.as_dict()
+        return self.stats
+
+    def fetch(self, first=0, count=None):
+        """-> (kmers uint64[count], list_off uint64[count + 1], tids uint32[list_off[-1]])"""
+        n = self.stats["records"] - first if count is None else count
+        km = np.zeros(n, dtype=np.uint64)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self.lib.lmat_export_fetch(self.h, first, n, _ptr(km), _ptr(off), None, 0))
+        td = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        self._chk(self.lib.lmat_export_fetch(self.h, first, n, None, None, _ptr(td), td.size))
+        return km, off, td[:int(off[-1])]
+
+    def taxid_counts(self):
+        """-> (taxids uint32[n] ascending, counts uint64[n]): lists that hold each taxid"""
+        n = C.c_uint64(0)
+        rc = self.lib.lmat_export_taxid_counts(self.h, None, None, 0, C.byref(n))
+        if rc != 0 and n.value == 0:
+            self._chk(rc)
+        tids = np.zeros(max(n.value, 1), dtype=np.uint32)
+        cnts = np.zeros(max(n.value, 1), dtype=np.uint64)
+        self._chk(self.lib.lmat_export_taxid_counts(self.h, _ptr(tids), _ptr(cnts), n.value, C.byref(n)))
+        return tids[:n.value], cnts[:n.value]
+
+    def close(self):
+        if self.h:
+            self.lib.lmat_export_destroy(self.h)
             self.h = None
 
 
@@ -626,6 +701,29 @@ class Engine:
             return c.report(), st
         finally:
             c.close()
+
+    # the database back out (lmat_export_*) ----------------------------------------------
+    def export_taxhisto(self, out=None, budget_bytes=0, prefix_bits=-1):
+        """The loaded database as tax_histo records, ascending, lists in stored order.  With `out` the file build_db reads is
+        written and the statistics (dict) returned; with out=None -> (statistics, (kmers, list_off, tids))."""
+        x = Export(self)
+        try:
+            x.set_options(budget_bytes, prefix_bits)
+            st = x.run(out)
+            return st if out else (st, x.fetch())
+        finally:
+            x.close()
+
+    def db_taxid_counts(self, budget_bytes=0, prefix_bits=-1):
+        """frequency_counter on the loaded database: -> {"counts": {taxid: lists that hold it}, "total_tid": n, "singletons": n}"""
+        x = Export(self)
+        try:
+            x.set_options(budget_bytes, prefix_bits)
+            st = x.run("")
+            t, c = x.taxid_counts()
+            return {"counts": {int(a): int(b) for a, b in zip(t, c)}, "total_tid": st["entries"], "singletons": st["singletons"]}
+        finally:
+            x.close()
 
     def load_image(self, path, table_bytes=0):
         self._chk(self.lib.lmat_db_load_image(self.ctx, path.encode(), table_bytes))

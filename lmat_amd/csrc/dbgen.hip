@@ -21,6 +21,8 @@
 //   union_classify (one-source runs are sized, gathered sets beyond 64 entries get a side-buffer segment, sorted by segment),
 //   union_kernel<count>, exclusive scan, union_kernel<write>: a one-source list is copied, the others are the closure of the union
 //   of the stored entries taken as owners -- the same virtual-tree walk over the entries in Euler-tour order, equal neighbours dropped.
+// A loaded database is one more such input (lmat_build_add_db): exported into host memory by dbexport.hip when it is added,
+// its records then go through input_record like a parsed file's.
 // hist_kernel counts, for either kind of run, the result records whose list holds each taxid (countTaxidFrequency's map).
 //
 // Written once for both: the walk (closure_walk, over a sequence accessor: OwnerSeq for the build, TourSeq for the merge) with claim_long,
@@ -695,6 +697,33 @@ void add_record(lmat_build* b, u32 taxid) {
 
 int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry);
 
+// Record i of an input -- of a parsed file, or of a loaded database (lmat_build_add_db) -- into `in`: its n taxids (4 bytes each, unaligned)
+// as dense node indices in stored order; every one must be in the tree and none may repeat.  A record without a list carries nothing.
+int input_record(lmat_build* b, lmat_build::Input& in, const std::string& name, u64 i, u64 km, const uint8_t* tid_bytes, u32 n, std::vector<u32>& chk) {
+    if (!n) return LMAT_OK;
+    const size_t at = in.nodes.size();
+    in.nodes.resize(at + n);
+    for (u32 j = 0; j < n; ++j) {
+        u32 t;
+        memcpy(&t, tid_bytes + 4 * (size_t)j, 4);
+        auto it = b->node_of.find(t);
+        if (it == b->node_of.end()) {
+            in.nodes.resize(at);
+            return berr(b, LMAT_E_TAXONOMY, name + ": taxid " + std::to_string(t) + " of record " + std::to_string(i) + " is not in the taxonomy tree");
+        }
+        in.nodes[at + j] = it->second;
+    }
+    if (n > 1) {
+        chk.assign(in.nodes.begin() + at, in.nodes.end());
+        std::sort(chk.begin(), chk.end());
+        auto dup = std::adjacent_find(chk.begin(), chk.end());
+        if (dup != chk.end()) return berr(b, LMAT_E_IO, name + ": taxid " + std::to_string(b->node_tid[*dup]) + " repeated in the list of record " + std::to_string(i));
+    }
+    in.kmers.push_back(km);
+    in.off.push_back(in.nodes.size());
+    return LMAT_OK;
+}
+
 // KmerFileMetaData.cpp:16-31 + tax_histo.cpp:250-266, as dbbuild.cpp reads it -- but strict: the header's count of records must be there
 int parse_taxhisto(lmat_build* b, const char* fn, lmat_build::Input& in) {
     const std::string name(fn);
@@ -735,25 +764,7 @@ int parse_taxhisto(lmat_build* b, const char* fn, lmat_build::Input& in) {
         if (i && km <= prev) return berr(b, LMAT_E_IO, name + ": k-mers not strictly ascending at record " + std::to_string(i));
         prev = km;
         if (end - pos < (size_t)n * 4) return berr(b, LMAT_E_IO, name + ": truncated taxid list in record " + std::to_string(i));
-        if (n) {
-            const size_t at = in.nodes.size();
-            in.nodes.resize(at + n);
-            for (u32 j = 0; j < n; ++j) {
-                u32 t;
-                memcpy(&t, &buf[pos + 4 * (size_t)j], 4);
-                auto it = b->node_of.find(t);
-                if (it == b->node_of.end()) return berr(b, LMAT_E_TAXONOMY, name + ": taxid " + std::to_string(t) + " of record " + std::to_string(i) + " is not in the taxonomy tree");
-                in.nodes[at + j] = it->second;
-            }
-            if (n > 1) {
-                chk.assign(in.nodes.begin() + at, in.nodes.end());
-                std::sort(chk.begin(), chk.end());
-                auto dup = std::adjacent_find(chk.begin(), chk.end());
-                if (dup != chk.end()) return berr(b, LMAT_E_IO, name + ": taxid " + std::to_string(b->node_tid[*dup]) + " repeated in the list of record " + std::to_string(i));
-            }
-            in.kmers.push_back(km);      // a record without a list carries nothing
-            in.off.push_back(in.nodes.size());
-        }
+        if (const int rc = input_record(b, in, name, i, km, &buf[pos], n, chk)) return rc;
         pos += (size_t)n * 4;
         if ((i + 1) % 1500 == 0) {
             if (end - pos < 8 || memcmp(&buf[pos], &test, 8) != 0) return berr(b, LMAT_E_IO, name + ": tax_histo sanity word missing after record " + std::to_string(i));
@@ -866,6 +877,41 @@ int lmat_build_add_taxhisto(lmat_build* b, const char* fn) {
     lmat_build::Input in;
     const int rc = parse_taxhisto(b, fn, in);
     if (rc) return rc;
+    b->inputs.push_back(std::move(in));
+    b->done = false;
+    return LMAT_OK;
+}
+
+// A loaded database as an input: exported into host memory now (dbexport.hip), its records then take input_record's path like a file's
+int lmat_build_add_db(lmat_build* b, lmat_ctx* src) {
+    if (!b || !src) return LMAT_E_ARG;
+    if (b->inputs.size() >= 0xFFFFu) return berr(b, LMAT_E_CAPACITY, "at most 65535 tax_histo inputs");
+    if (src->gene_mode) return berr(b, LMAT_E_ARG, "a gene database holds gene ids, not taxids: it is no input of a merge");
+    if (src->db_ready && src->dev.k != b->k)
+        return berr(b, LMAT_E_ARG, "k-mer length " + std::to_string(src->dev.k) + " of the loaded database differs from the builder's " + std::to_string(b->k));
+    lmat_export* x = nullptr;
+    int rc = lmat_export_create(src, &x);
+    if (rc) return berr(b, rc, lmat_last_error(src));
+    lmat_export_stats xs;
+    rc = lmat_export_set_options(x, b->budget, -1);
+    if (!rc) rc = lmat_export_run(x, nullptr, &xs);
+    std::vector<uint64_t> km, off;
+    std::vector<uint32_t> td;
+    if (!rc) {
+        km.resize(xs.records);
+        off.resize(xs.records + 1);
+        td.resize(std::max<u64>(xs.entries, 1));
+        rc = lmat_export_fetch(x, 0, xs.records, km.data(), off.data(), td.data(), td.size());
+    }
+    if (rc) berr(b, rc, std::string("loaded database: ") + lmat_export_error(x));
+    lmat_export_destroy(x);
+    if (rc) return rc;
+    lmat_build::Input in;
+    in.fn = "loaded database";
+    in.off.assign(1, 0);
+    std::vector<u32> chk;
+    for (u64 i = 0; i < km.size(); ++i)
+        if ((rc = input_record(b, in, in.fn, i, km[i], reinterpret_cast<const uint8_t*>(td.data() + off[i]), (u32)(off[i + 1] - off[i]), chk))) return rc;
     b->inputs.push_back(std::move(in));
     b->done = false;
     return LMAT_OK;

@@ -1,4 +1,5 @@
-// kmer_dev.hpp -- what the k-mer pipelines on the device share (dbgen.hip: the database builder; kcov.hip: the per-group k-mer coverage).
+// kmer_dev.hpp -- what the k-mer pipelines on the device share (dbgen.hip: the database builder; kcov.hip: the per-group k-mer coverage;
+// dbexport.hip: the export of a loaded database, which uses the wave helpers and the host part).
 //   device: the wave helpers and the two phases of the text scan -- a wave's 1024 bytes packed into LDS (pack_span), the canonical
 //           k-mer of the window that ends at one byte of them (window_kmer) -- and the record of a text position (span_records / record_at);
 //   host:   with_temp (rocPRIM's two calls) and LapTimer (HIP-event time per stage); DevBuf and ensure_all come from devbuf.hpp.

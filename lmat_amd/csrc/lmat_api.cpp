@@ -2399,6 +2399,14 @@ int lmat_table_address(int k, uint64_t want_buckets, uint64_t kmer, uint64_t* n_
     return LMAT_OK;
 }
 
+int lmat_table_unaddress(int k, uint64_t want_buckets, uint32_t bucket, uint32_t tag, uint64_t* kmer) {
+    const CptGeom g = cpt_geometry(k, want_buckets);
+    if (!g.nb || !kmer) return LMAT_E_ARG;
+    if (bucket >= g.nb || tag == 0 || tag > 0xFFFFu || ((tag - 1) >> 9) >= ((uint32_t)g.W << g.lowbits)) return LMAT_E_ARG;
+    *kmer = cpt_unaddress(g, bucket, tag);
+    return LMAT_OK;
+}
+
 int64_t lmat_format_out(const lmat_ctx* c, const lmat_read_result* results, uint64_t n, const lmat_cand* cands,
                         const uint8_t* bases, const uint64_t* off, int prn_read, uint64_t first_index, char* buf,
                         uint64_t cap) {

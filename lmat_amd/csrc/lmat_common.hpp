@@ -185,6 +185,35 @@ LM_HD void cpt_address(const CptGeom& g, uint64_t c, uint64_t cr, uint32_t& buck
     tag = 1 + (((((rho << g.lowbits) | low) * 4 + (uint32_t)j) * 2 + ((uint32_t)best & 1u)) * 64 + other);
 }
 
+// cpt_feistel run backwards: the same four rounds, last first
+LM_HD uint64_t cpt_feistel_inv(uint64_t x, int m, uint32_t ka, uint32_t kb, uint32_t kc, uint32_t kd) {
+    const uint32_t mm = (1u << m) - 1;
+    uint32_t L = (uint32_t)(x >> m), R = (uint32_t)x & mm;
+    R ^= (LM_MUL24(L, kd) >> 7) & mm;
+    L ^= (LM_MUL24(R, kc) >> 7) & mm;
+    R ^= (LM_MUL24(L, kb) >> 7) & mm;
+    L ^= (LM_MUL24(R, ka) >> 7) & mm;
+    return ((uint64_t)L << m) | R;
+}
+LM_HD uint64_t cpt_unscramble(uint64_t y, int m) { return cpt_feistel_inv(y, m, 0x6A09u, 0x3B67u, 0x5F1Du, 0x7C15u); }
+LM_HD uint64_t cpt_unmix(uint64_t s, int m) { return cpt_feistel_inv(s, m, 0x52DBu, 0x4F6Du, 0x6E2Bu, 0x35A7u); }
+
+// bucket and tag (tag != 0) of an occupied slot -> the canonical k-mer filed there: cpt_address read backwards (the export of a table)
+LM_HD uint64_t cpt_unaddress(const CptGeom& g, uint32_t bucket, uint32_t tag) {
+    const int m = g.m;
+    const uint32_t t = tag - 1;
+    const uint32_t other = t & 63u, strand = (t >> 6) & 1u, rl = t >> 9;
+    const int j = (int)(t >> 7) & 3;
+    const uint32_t rho = rl >> g.lowbits, low = rl & ((1u << g.lowbits) - 1);
+    uint64_t hi;
+    if (g.wshift == -2) hi = (((uint64_t)bucket << 32) + g.nb - 1) / g.nb + rho;  // the rho-th hi with hi * nb >> 32 == bucket
+    else hi = (uint64_t)bucket * g.W + rho;
+    const uint64_t y = cpt_unscramble(cpt_unmix((hi << g.lowbits) | low, m), m);   // the minimizer: the smaller of the m-mer pair
+    const uint64_t x = strand ? revcomp_fwd(y, m) : y;                               // the m-mer at place j of the canonical k-mer
+    const int rs = 2 * (kCptW - 1 - j);
+    return ((uint64_t)(other >> rs) << (2 * m + rs)) | (x << rs) | (uint64_t)(other & ((1u << rs) - 1));
+}
+
 // ---- packed read record (4-byte words) ---------------------------------------------------
 //   word 0: length in bases; then ceil(len/16) words of 2-bit codes (base j at bits 2*(j%16)),
 //   then ceil(len/32) words of validity bits (1 = ACGT).
