@@ -469,6 +469,35 @@ int lmat_export_taxid_counts(lmat_export* e, uint32_t* tids, uint64_t* counts, u
  * the call and its records take the path a parsed file takes.  k must match (LMAT_E_ARG); a gene database is LMAT_E_ARG. */
 int lmat_build_add_db(lmat_build* b, lmat_ctx* src);
 
+/* ---- gene databases from gene FASTA: the id-set mode of the builder ----
+ * What a gene database is, is what kmerPrefixCounter computes before tax_histo touches it (hash[kmer].insert(gid),
+ * src/kmerPrefixCounter.cpp:114-147): per canonical k-mer the set of ids of the records that hold it.  lmat_genebuild_create
+ * returns an lmat_build WITHOUT A TAXONOMY; every lmat_build_* entry point works on it, and the file it writes is the one
+ * lmat_genedb_begin + lmat_db_add_taxhisto read (gene_label -d).
+ *   result   for every canonical k-mer of the inputs the ids of the records that contain it, every id once, in ASCENDING NUMERIC
+ *            order; records in ascending k-mer order.  No closure, nothing is looked up anywhere.
+ *   input    FASTA as lmat_build_add_fasta reads it (">" + decimal id) or lmat_build_add_sequence.  Ids are 1 .. 2^32-1: a header
+ *            of 0 (the result records' "no gene") or of a value beyond 32 bits is LMAT_E_IO naming the line, and the file adds
+ *            nothing; lmat_build_add_sequence with id 0 is LMAT_E_ARG.  Records of one id are one owner.  A record shorter than
+ *            k, an empty one and one without a valid base contribute nothing and are no errors.
+ *   merge    lmat_build_add_taxhisto takes tax_histo-format files of gene ids (a fixture, an earlier output, an export): per
+ *            k-mer the result is the union of the ids of every source that holds it, ascending -- so a one-source list is that
+ *            list SORTED.  An id repeated inside one list and an id 0 are LMAT_E_IO; the other file checks are those of section
+ *            10.  lmat_build_add_db takes a gene context (lmat_genedb_begin); a taxonomy context is LMAT_E_ARG, as a gene context
+ *            stays for a tree-mode builder.  The inputs' entries of a prefix pass are (k-mer, owner) pairs beside the extracted
+ *            ones; the derived prefix_bits accounts for them, a forced one that does not hold them is LMAT_E_CAPACITY.  Output
+ *            bytes do not depend on prefix_bits, the budget, chunk_bases or the order in which inputs were added.
+ *   errors   a list of more than 65535 ids: LMAT_E_CAPACITY from lmat_build_run, never cut short.
+ *   stats    lmat_build_stats keeps its layout: dropped_unknown is 0, closure_ms holds the list stage, distinct_kmers counts the
+ *            result's k-mers (inputs included).  lmat_merge_stats: a source is a file or the text; records_grown is 0 and only
+ *            upload_ms is filled (the inputs ride in the build's own sort).  lmat_build_taxid_counts gives, per id, the number
+ *            of result records whose list holds it: the gene's k-mer count.
+ * lmat_genedb_build_from_genes is the counterpart of lmat_db_build_from_genomes: ctx is a fresh context (no taxonomy needed) and
+ * ends holding the table lmat_genedb_begin / lmat_db_add_taxhisto / lmat_db_finalize build from the written file.  A tree-mode
+ * builder passed to it, or an id-set builder passed to lmat_db_build_from_genomes, is LMAT_E_ARG. */
+int lmat_genebuild_create(lmat_ctx* ctx, int k, lmat_build** out);
+int lmat_genedb_build_from_genes(lmat_ctx* ctx, lmat_build* b, uint64_t table_bytes);
+
 /* ---- per-group k-mer coverage of a set of reads (content_summ's counting, src/content_summ.cpp:113-152, 538-571) ----
  * Input: reads (ASCII, any length, 0 included) with a caller-chosen 32-bit group id each -- content_summ uses the taxid it counts
  * the read under -- and a list of k sizes in 1..31 (duplicates allowed, reported per index).

@@ -204,6 +204,8 @@ def load_library(path: str | None = None):
         "lmat_export_fetch": (i32, [vp, u64, u64, vp, vp, vp, u64]),
         "lmat_export_taxid_counts": (i32, [vp, vp, vp, u64, P(u64)]),
         "lmat_build_add_db": (i32, [vp, vp]),
+        "lmat_genebuild_create": (i32, [vp, i32, P(vp)]),
+        "lmat_genedb_build_from_genes": (i32, [vp, vp, u64]),
         "lmat_table_unaddress": (i32, [i32, u64, u32, u32, P(u64)]),
     }
     for name, (res, args) in sig.items():
@@ -234,7 +236,8 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_cov_create", "lmat_cov_destroy", "lmat_cov_error", "lmat_cov_set_options", "lmat_cov_add_reads", "lmat_cov_run",
             "lmat_cov_summary", "lmat_cov_histogram",
             "lmat_export_create", "lmat_export_destroy", "lmat_export_error", "lmat_export_set_options", "lmat_export_run", "lmat_export_fetch",
-            "lmat_export_taxid_counts", "lmat_build_add_db", "lmat_table_unaddress"]
+            "lmat_export_taxid_counts", "lmat_build_add_db", "lmat_table_unaddress",
+            "lmat_genebuild_create", "lmat_genedb_build_from_genes"]
 
 
 def _ptr(a):
@@ -392,12 +395,18 @@ class Stream:
 
 
 class Builder:
-    """lmat_build: genome FASTA + taxonomy tree -> k-mers with LCA-closed taxid lists, on the GPU of `eng`."""
+    """lmat_build: genome FASTA + taxonomy tree -> k-mers with LCA-closed taxid lists, on the GPU of `eng`.
+    genes=True (and no tree): the id-set mode -- gene FASTA -> k-mers with the ascending ids of the records that hold them."""
 
-    def __init__(self, eng, k, tree):
+    def __init__(self, eng, k, tree=None, genes=False):
         self.eng, self.lib = eng, eng.lib
         h = C.c_void_p()
-        eng._chk(self.lib.lmat_build_create(eng.ctx, k, tree.encode(), C.byref(h)))
+        if genes:
+            if tree is not None:
+                raise ValueError("an id-set builder takes no taxonomy tree")
+            eng._chk(self.lib.lmat_genebuild_create(eng.ctx, k, C.byref(h)))
+        else:
+            eng._chk(self.lib.lmat_build_create(eng.ctx, k, tree.encode() if tree is not None else None, C.byref(h)))
         self.h = h
         self.stats = None
 
@@ -646,8 +655,8 @@ class Engine:
         self._chk(self.lib.lmat_db_finalize(self.ctx))
 
     # the database from genomes (lmat_build_*) ---------------------------------------
-    def _builder(self, fastas, tree, k, budget_bytes=0, prefix_bits=-1, chunk_bases=0, taxhistos=()):
-        b = Builder(self, k, tree)
+    def _builder(self, fastas, tree, k, budget_bytes=0, prefix_bits=-1, chunk_bases=0, taxhistos=(), genes=False):
+        b = Builder(self, k, tree, genes=genes)
         try:
             b.set_options(budget_bytes, prefix_bits, chunk_bases)
             for f in ([fastas] if isinstance(fastas, str) else fastas or ()):
@@ -686,6 +695,26 @@ class Engine:
         b = self._builder(fastas, tree, k, **opts)
         try:
             self._chk(self.lib.lmat_db_build_from_genomes(self.ctx, b.h, int(table_bytes)))
+            return b.stats
+        finally:
+            b.close()
+
+    # gene databases from gene FASTA: the builder's id-set mode (lmat_genebuild_create) ----------
+    def build_gene_taxhisto(self, fastas, k, out, taxhistos=(), **opts):
+        """Gene FASTA file(s) ('>' + gene id headers) and/or existing gene tax_histo files -> the gene database file `out`
+        (what build_gene_db and gene_label -d read).  opts as build_taxhisto.  -> statistics (dict), the merge's under "merge"."""
+        b = self._builder(fastas, None, k, taxhistos=taxhistos, genes=True, **opts)
+        try:
+            b.write_taxhisto(out)
+            return {**b.stats, "merge": b.merge_stats}
+        finally:
+            b.close()
+
+    def build_gene_db_from_genes(self, fastas, k=20, table_bytes=0, taxhistos=(), **opts):
+        """The gene classify table straight from gene FASTA, no file in between and no taxonomy -> statistics."""
+        b = self._builder(fastas, None, k, taxhistos=taxhistos, genes=True, **opts)
+        try:
+            self._chk(self.lib.lmat_genedb_build_from_genes(self.ctx, b.h, int(table_bytes)))
             return b.stats
         finally:
             b.close()

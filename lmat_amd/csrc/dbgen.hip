@@ -25,6 +25,11 @@
 // its records then go through input_record like a parsed file's.
 // hist_kernel counts, for either kind of run, the result records whose list holds each taxid (countTaxidFrequency's map).
 //
+// The id-set mode (lmat_genebuild_create, DESIGN section 13: gene databases) stops where kmerPrefixCounter does: no tree, no closure.  Owner
+// indices are the ranks of the ids among all ids of the run, so idlist_kernel<count / write> (in closure_kernel's place) writes id_of[owner]
+// in order; tax_histo inputs are not a second stage there -- their entries of a pass join the extracted pairs before the sort, marked by one
+// flag bit below the owner (text_runs_kernel reads it back for the merge statistics).
+//
 // Written once for both: the walk (closure_walk, over a sequence accessor: OwnerSeq for the build, TourSeq for the merge) with claim_long,
 // count_list and rank_store around it on the device; on the host the count -> CSR tail (write_lists) and write_records.  The text scan of the
 // extraction, the wave helpers, DevBuf, with_temp and LapTimer are kmer_dev.hpp's, shared with kcov.hip.
@@ -59,6 +64,7 @@ struct ExtractArgs {
     const u32* rec_owner;    // [n_rec]
     u32 n_rec;
     int k, prefix_bits, owner_bits;   // owner_bits >= 0: key = k-mer << owner_bits | owner; -1: separate arrays
+    int flag_bits;           // 1: one more bit below the owner, 0 for a pair from text (id mode with tax_histo inputs, whose pairs carry 1)
     u32 pass;
     u64* keys;
     u32* vals;
@@ -108,8 +114,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void extract_kernel(ExtractArg
                 const u64 pos = a.chunk_lo + wbase + q;
                 const u32 owner = a.rec_owner[record_at(a.rec_start, rlo, rhi, pos)];
                 const u64 dst = base + __popcll(bal & ((1ull << lane) - 1));
-                if (a.owner_bits >= 0) a.keys[dst] = (canon << a.owner_bits) | owner;
-                else { a.keys[dst] = canon; a.vals[dst] = owner; }
+                if (a.owner_bits >= 0) a.keys[dst] = ((canon << a.owner_bits) | owner) << a.flag_bits;
+                else { a.keys[dst] = canon; a.vals[dst] = owner << a.flag_bits; }
             }
         }
     }
@@ -121,10 +127,12 @@ struct Sorted {   // the sorted pairs, either packing
     const u64* keys;
     const u32* vals;
     int owner_bits;
+    int flag_bits;   // the source flag below the owner (ExtractArgs)
     __device__ __forceinline__ void get(u64 i, u64& km, u32& ow) const {
-        if (owner_bits >= 0) { const u64 x = keys[i]; km = x >> owner_bits; ow = (u32)(x & ((1ull << owner_bits) - 1)); }
-        else { km = keys[i]; ow = vals[i]; }
+        if (owner_bits >= 0) { const u64 x = keys[i] >> flag_bits; km = x >> owner_bits; ow = (u32)(x & ((1ull << owner_bits) - 1)); }
+        else { km = keys[i]; ow = vals[i] >> flag_bits; }
     }
+    __device__ __forceinline__ bool from_text(u64 i) const { return !(((owner_bits >= 0) ? (u32)keys[i] : vals[i]) & (u32)flag_bits); }
 };
 
 // flag[i] = (head of a run of one k-mer) << 32 | (first of equal (k-mer, owner) pairs)
@@ -345,6 +353,64 @@ __global__ __launch_bounds__(256) void long_copy_kernel(const u32* sorted, const
     const u32 b = long_begin[q], n = long_end[q] - b;
     u32* dst = tids + off[long_run[q]];
     for (u32 i = threadIdx.x; i < n; i += blockDim.x) dst[i] = sorted[b + i];
+}
+
+// ------------------------------------------------------------------------------------------------------------ id-set mode
+// No tree and no closure (lmat_genebuild_create): the list of a run is the ids of its distinct owners.  Owner indices are the ranks of the
+// ids among all ids of the run's inputs, so the owners of a run arrive in ascending id order and the list is id_of[owner] in order.
+struct IdListArgs {
+    u32 R;
+    const u32* run_start;    // [R + 1]
+    const u32* d_owner;      // distinct owners of every run, ascending
+    const u32* id_of;        // [n_owner] ascending
+    u64* cnt;                // count pass: [R]
+    const u64* off;          // write pass: [R + 1]
+    u32* tids;               // write pass: the CSR
+    u64* counters;
+};
+
+// One run per lane.  Count: the number of distinct pairs of the run.  Write: runs of up to 64 entries are written by their lanes, the longer
+// ones one after the other by the whole wave.  Nothing here feeds the side buffers of the long lists: the order is there already.
+template <bool WRITE>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void idlist_kernel(IdListArgs a) {
+    const u32 lane = lane_id();
+    const u64 r64 = ((u64)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 64 + lane;
+    const bool active = r64 < a.R;
+    const u32 r = active ? (u32)r64 : 0;
+    u32 s = 0, n = 0;
+    if (active) { s = a.run_start[r]; n = a.run_start[r + 1] - s; }
+    if (!WRITE) {
+        if (active) a.cnt[r] = n;
+        const u64 entries = wave_sum<u64>(n);
+        const u32 longest = wave_max<u32>(n);
+        const u32 singles = __popcll(__ballot(n == 1));
+        if (lane == 0 && entries) {
+            atomicAdd(&a.counters[C_ENTRIES], entries);
+            atomicMax(&a.counters[C_LONGEST], (u64)longest);
+            if (singles) atomicAdd(&a.counters[C_SINGLETONS], (u64)singles);
+            if (longest > kMaxList) atomicMax(&a.counters[C_TOOLONG], (u64)longest);
+        }
+        return;
+    }
+    u64 o = 0;
+    if (active) {
+        o = a.off[r];
+        if (n <= 64) for (u32 i = 0; i < n; ++i) a.tids[o + i] = a.id_of[a.d_owner[s + i]];
+    }
+    u64 wide = __ballot(n > 64);
+    while (wide) {
+        const int b = __ffsll((long long)wide) - 1;
+        wide &= wide - 1;
+        const u32 rs = __shfl(s, b), rn = __shfl(n, b);
+        const u64 ro = ((u64)__shfl((u32)(o >> 32), b) << 32) | __shfl((u32)o, b);
+        for (u32 i = lane; i < rn; i += 64) a.tids[ro + i] = a.id_of[a.d_owner[rs + i]];
+    }
+}
+
+// has_text[r] = 1 when a pair of run r came from text (its flag bit is 0); flag / pos are those of seg_flag_kernel and its scan
+__global__ __launch_bounds__(256) void text_runs_kernel(Sorted s, u64 n, const u64* flag, const u64* pos, u32* has_text) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && s.from_text(i)) has_text[(u32)(pos[i] >> 32) + (u32)(flag[i] >> 32) - 1] = 1u;
 }
 
 // ---------------------------------------------------------------------------------------------- merge of tax_histo inputs
@@ -580,6 +646,7 @@ struct LongBufs {   // the side buffers of the lists beyond 64 entries
 struct lmat_build {
     lmat_ctx* ctx = nullptr;
     int k = 0;
+    bool id_mode = false;                // lmat_genebuild_create: no tree; node_tid is the ascending ids of all inputs, set by every run
     std::string err;
     // taxonomy, dense: index = rank of the taxid among the tree's node ids
     std::vector<u32> node_tid, parent, depth, tin;
@@ -604,7 +671,7 @@ struct lmat_build {
         std::string fn;
         std::vector<u64> kmers;          // strictly ascending
         std::vector<u64> off;            // [records + 1]
-        std::vector<u32> nodes;
+        std::vector<u32> nodes;          // id mode: the ids as stored
     };
     std::vector<Input> inputs;
     lmat_merge_stats mstats;
@@ -724,6 +791,25 @@ int input_record(lmat_build* b, lmat_build::Input& in, const std::string& name, 
     return LMAT_OK;
 }
 
+// id mode: the n ids as stored; none is looked up, none may be 0 or repeat
+int input_record_ids(lmat_build* b, lmat_build::Input& in, const std::string& name, u64 i, u64 km, const uint8_t* tid_bytes, u32 n, std::vector<u32>& chk) {
+    if (!n) return LMAT_OK;
+    chk.resize(n);
+    memcpy(chk.data(), tid_bytes, 4 * (size_t)n);
+    in.nodes.insert(in.nodes.end(), chk.begin(), chk.end());
+    std::sort(chk.begin(), chk.end());
+    if (chk[0] == 0) return berr(b, LMAT_E_IO, name + ": id 0 in the list of record " + std::to_string(i));
+    auto dup = std::adjacent_find(chk.begin(), chk.end());
+    if (dup != chk.end()) return berr(b, LMAT_E_IO, name + ": id " + std::to_string(*dup) + " repeated in the list of record " + std::to_string(i));
+    in.kmers.push_back(km);
+    in.off.push_back(in.nodes.size());
+    return LMAT_OK;
+}
+
+int any_record(lmat_build* b, lmat_build::Input& in, const std::string& name, u64 i, u64 km, const uint8_t* tid_bytes, u32 n, std::vector<u32>& chk) {
+    return b->id_mode ? input_record_ids(b, in, name, i, km, tid_bytes, n, chk) : input_record(b, in, name, i, km, tid_bytes, n, chk);
+}
+
 // KmerFileMetaData.cpp:16-31 + tax_histo.cpp:250-266, as dbbuild.cpp reads it -- but strict: the header's count of records must be there
 int parse_taxhisto(lmat_build* b, const char* fn, lmat_build::Input& in) {
     const std::string name(fn);
@@ -764,7 +850,7 @@ int parse_taxhisto(lmat_build* b, const char* fn, lmat_build::Input& in) {
         if (i && km <= prev) return berr(b, LMAT_E_IO, name + ": k-mers not strictly ascending at record " + std::to_string(i));
         prev = km;
         if (end - pos < (size_t)n * 4) return berr(b, LMAT_E_IO, name + ": truncated taxid list in record " + std::to_string(i));
-        if (const int rc = input_record(b, in, name, i, km, &buf[pos], n, chk)) return rc;
+        if (const int rc = any_record(b, in, name, i, km, &buf[pos], n, chk)) return rc;
         pos += (size_t)n * 4;
         if ((i + 1) % 1500 == 0) {
             if (end - pos < 8 || memcmp(&buf[pos], &test, 8) != 0) return berr(b, LMAT_E_IO, name + ": tax_histo sanity word missing after record " + std::to_string(i));
@@ -813,6 +899,21 @@ int lmat_build_create(lmat_ctx* ctx, int k, const char* tree_fn, lmat_build** ou
     return LMAT_OK;
 }
 
+int lmat_genebuild_create(lmat_ctx* ctx, int k, lmat_build** out) {
+    if (!out) return LMAT_E_ARG;
+    *out = nullptr;
+    if (!ctx) return LMAT_E_ARG;
+    if (k < 1 || k > 20) return lmat::set_err(ctx, LMAT_E_ARG, "k must be in 1..20 (40-bit keys)");
+    lmat_build* b = new lmat_build();
+    b->ctx = ctx;
+    b->k = k;
+    b->id_mode = true;
+    memset(&b->stats, 0, sizeof(b->stats));
+    memset(&b->mstats, 0, sizeof(b->mstats));
+    *out = b;
+    return LMAT_OK;
+}
+
 void lmat_build_destroy(lmat_build* b) { delete b; }
 const char* lmat_build_error(const lmat_build* b) { return b ? b->err.c_str() : "null build"; }
 
@@ -827,6 +928,7 @@ int lmat_build_set_options(lmat_build* b, uint64_t device_budget_bytes, int pref
 
 int lmat_build_add_sequence(lmat_build* b, uint32_t taxid, const uint8_t* ascii, uint64_t n) {
     if (!b || (!ascii && n)) return LMAT_E_ARG;
+    if (b->id_mode && taxid == 0) return berr(b, LMAT_E_ARG, "id 0 stands for no gene: ids are 1 .. 2^32-1");
     add_record(b, taxid);
     for (u64 i = 0; i < n; ++i)
         if (ascii[i] != '\n' && ascii[i] != '\r') { b->text.push_back(ascii[i]); ++b->bases; }
@@ -846,6 +948,8 @@ int lmat_build_add_fasta(lmat_build* b, const char* fn) {
     bool open = false;
     u64 lineno = 0;
     int rc = LMAT_OK;
+    const size_t text0 = b->text.size(), rec0 = b->rec_start.size();   // id mode: a file that fails adds nothing
+    const u64 bases0 = b->bases;
     while ((len = getline(&line, &cap, f)) >= 0) {
         ++lineno;
         while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) --len;
@@ -854,6 +958,13 @@ int lmat_build_add_fasta(lmat_build* b, const char* fn) {
             if (len < 2 || line[1] < '0' || line[1] > '9') {
                 rc = berr(b, LMAT_E_IO, std::string("bad FASTA header (want '>' + decimal taxid) at line ") + std::to_string(lineno) + " of " + fn);
                 break;
+            }
+            if (b->id_mode) {   // 1 .. 2^32-1: 0 is "no gene" in the result records, a wider value would wrap
+                const unsigned long long v = strtoull(line + 1, nullptr, 10);
+                if (v == 0 || v > 0xFFFFFFFFull) {
+                    rc = berr(b, LMAT_E_IO, std::string("gene id out of 1 .. 4294967295 in the FASTA header at line ") + std::to_string(lineno) + " of " + fn);
+                    break;
+                }
             }
             if (open) b->text.push_back('\n');
             add_record(b, (u32)strtoul(line + 1, nullptr, 10));
@@ -867,6 +978,12 @@ int lmat_build_add_fasta(lmat_build* b, const char* fn) {
     if (open) b->text.push_back('\n');
     free(line);
     fclose(f);
+    if (rc && b->id_mode) {
+        b->text.resize(text0);
+        b->rec_start.resize(rec0);
+        b->rec_taxid.resize(rec0);
+        b->bases = bases0;
+    }
     b->done = false;
     return rc;
 }
@@ -886,7 +1003,8 @@ int lmat_build_add_taxhisto(lmat_build* b, const char* fn) {
 int lmat_build_add_db(lmat_build* b, lmat_ctx* src) {
     if (!b || !src) return LMAT_E_ARG;
     if (b->inputs.size() >= 0xFFFFu) return berr(b, LMAT_E_CAPACITY, "at most 65535 tax_histo inputs");
-    if (src->gene_mode) return berr(b, LMAT_E_ARG, "a gene database holds gene ids, not taxids: it is no input of a merge");
+    if (src->gene_mode && !b->id_mode) return berr(b, LMAT_E_ARG, "a gene database holds gene ids, not taxids: it is no input of a merge");
+    if (!src->gene_mode && b->id_mode) return berr(b, LMAT_E_ARG, "a taxonomy database holds taxids, not gene ids: it is no input of an id-set build");
     if (src->db_ready && src->dev.k != b->k)
         return berr(b, LMAT_E_ARG, "k-mer length " + std::to_string(src->dev.k) + " of the loaded database differs from the builder's " + std::to_string(b->k));
     lmat_export* x = nullptr;
@@ -911,7 +1029,7 @@ int lmat_build_add_db(lmat_build* b, lmat_ctx* src) {
     in.off.assign(1, 0);
     std::vector<u32> chk;
     for (u64 i = 0; i < km.size(); ++i)
-        if ((rc = input_record(b, in, in.fn, i, km[i], reinterpret_cast<const uint8_t*>(td.data() + off[i]), (u32)(off[i + 1] - off[i]), chk))) return rc;
+        if ((rc = any_record(b, in, in.fn, i, km[i], reinterpret_cast<const uint8_t*>(td.data() + off[i]), (u32)(off[i + 1] - off[i]), chk))) return rc;
     b->inputs.push_back(std::move(in));
     b->done = false;
     return LMAT_OK;
@@ -1065,7 +1183,7 @@ struct MergeState {
         tree = tree_;
         timer = timer_;
         n_nodes = (u32)b->node_tid.size();
-        merging = !b->inputs.empty();
+        merging = !b->inputs.empty() && !b->id_mode;   // id mode unites its inputs inside the build's own sort (BuildRun::slice_inputs)
         memset(&b->mstats, 0, sizeof(b->mstats));
         b->node_counts.assign(n_nodes, 0);
         BHIP(b, hist.ensure((size_t)n_nodes * 8));
@@ -1278,8 +1396,18 @@ struct BuildRun {
     // owners
     u32 n_rec = 0, n_owner = 0, n_known = 0;
     int ob = 1;                           // bits of an owner index
+    int fb = 0;                           // id mode with tax_histo inputs: the source flag below the owner (ExtractArgs::flag_bits)
     bool packed = true;                   // one 64-bit key per pair
     std::vector<u32> rec_owner, owner_node;
+    // id mode, tax_histo inputs: every entry's owner index; per pass the next record of every input, the slices taken and their pairs
+    std::vector<std::vector<u32>> in_owner;
+    std::vector<size_t> cursor;
+    struct Slice { size_t input, lo, hi; };
+    std::vector<Slice> slices;
+    std::vector<u64> in_keys;
+    std::vector<u32> in_vals;
+    u64 in_pairs = 0;
+    DevBuf has_text;
     // memory model
     u32 chunk = 0;
     u64 chunk_alloc = 0, cap = 0;
@@ -1297,6 +1425,24 @@ struct BuildRun {
 
     // owners: distinct taxids; the tree's own in Euler-tour order, the others behind them
     void number_owners() {
+        if (b->id_mode) {   // the owner of an id is its rank among the ids of all inputs (b->node_tid): sorting by (k-mer, owner) gives ascending ids
+            const std::vector<u32>& ids = b->node_tid;
+            auto rank = [&](u32 id) { return (u32)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin()); };
+            n_owner = n_known = (u32)ids.size();
+            rec_owner.resize(n_rec);
+            for (u32 r = 0; r < n_rec; ++r) rec_owner[r] = rank(b->rec_taxid[r]);
+            in_owner.resize(b->inputs.size());
+            for (size_t s = 0; s < b->inputs.size(); ++s) {
+                in_owner[s].resize(b->inputs[s].nodes.size());
+                for (size_t i = 0; i < in_owner[s].size(); ++i) in_owner[s][i] = rank(b->inputs[s].nodes[i]);
+            }
+            cursor.assign(b->inputs.size(), 0);
+            fb = b->inputs.empty() ? 0 : 1;
+            while ((1ull << ob) < n_owner) ++ob;
+            packed = 2 * b->k + ob + fb <= 64;
+            if (const char* e = getenv("LMAT_DBGEN_SORT")) if (!strcmp(e, "pairs")) packed = false;
+            return;
+        }
         std::vector<u32> owners(b->rec_taxid);
         std::sort(owners.begin(), owners.end());
         owners.erase(std::unique(owners.begin(), owners.end()), owners.end());
@@ -1335,7 +1481,7 @@ struct BuildRun {
         const u64 chunk_waves = ((u64)chunk + kSpan - 1) / kSpan;
         chunk_alloc = chunk_waves * kSpan + kLead + 64;
         const u64 fixed = chunk_alloc + (u64)n_rec * 12 + (u64)b->node_tid.size() * 12 + (u64)n_owner * 4 + (64u << 20);   // + sort scratch and slack
-        const u64 per_pair = 8 + 8 + 8 + 8 + 8 + 4 + 4 + (packed ? 0 : 8) + 16;   // keys x2, flag, pos, distinct pair, run start, (vals x2), list entries (estimate)
+        const u64 per_pair = 8 + 8 + 8 + 8 + 8 + 4 + 4 + (packed ? 0 : 8) + 16 + (fb ? 4 : 0);   // keys x2, flag, pos, distinct pair, run start, (vals x2), list entries (estimate), (text flag of a run)
         if (budget <= fixed || (budget <= fixed + per_pair * 1024 && T != 0)) return berr(b, LMAT_E_NOMEM, "device budget of " + std::to_string(budget) + " bytes is below the fixed buffers");
         cap = std::min<u64>((budget - fixed) / per_pair, 0x7FFFFF00ull);
         pb = pb_forced;
@@ -1344,6 +1490,25 @@ struct BuildRun {
             pb = pb_start;
             while (pb < std::min(2 * k, 24) && (double)T * 2.0 / (double)(1ull << pb) > (double)cap && T > cap) ++pb;
             if (pb == 0 && T > cap) pb = 1;
+        }
+        if (fb) {
+            // id mode: the inputs' entries of a pass are pairs beside the extracted ones, known exactly; the text shares what they leave of cap
+            const u64 cap_budget = cap;
+            const int pb_max = std::min(2 * k, 24);
+            for (pb = pb_forced < 0 ? pb_start : pb_forced;; ++pb) {
+                std::vector<u64> ent((size_t)1 << pb, 0);
+                for (const auto& in : b->inputs)
+                    for (size_t i = 0; i < in.kmers.size(); ++i) ent[pb ? (size_t)(in.kmers[i] >> (2 * k - pb)) : 0] += in.off[i + 1] - in.off[i];
+                const u64 in_max = *std::max_element(ent.begin(), ent.end());
+                const bool in_fit = in_max <= cap_budget;
+                const u64 room = in_fit ? cap_budget - in_max : 0;
+                const bool seq_fit = in_fit && (T <= room || (double)T * 2.0 / (double)(1ull << pb) <= (double)room);
+                cap = std::min<u64>(cap_budget, T + in_max);
+                if (in_fit && (seq_fit || pb_forced >= 0)) return LMAT_OK;   // a forced split that the text overflows is found by the extraction
+                if (pb_forced >= 0 || pb >= pb_max)
+                    return berr(b, LMAT_E_CAPACITY, "the tax_histo inputs hold " + std::to_string(in_max) + " entries in one of the " + std::to_string(1ull << pb) +
+                                                       " prefix passes, the device budget holds " + std::to_string(cap_budget) + " pairs: raise the budget or prefix_bits");
+            }
         }
         if (!b->inputs.empty()) {
             // The slices of the inputs are known exactly; what they take of a pass comes off the budget first, the pairs of the genomes share the rest
@@ -1376,14 +1541,51 @@ struct BuildRun {
         if (n_rec) {
             BHIP(b, hipMemcpyAsync(rec_start.p, b->rec_start.data(), (size_t)n_rec * 8, hipMemcpyHostToDevice, st));
             BHIP(b, hipMemcpyAsync(d_rec_owner.p, rec_owner.data(), (size_t)n_rec * 4, hipMemcpyHostToDevice, st));
-            BHIP(b, hipMemcpyAsync(d_owner_node.p, owner_node.data(), (size_t)n_owner * 4, hipMemcpyHostToDevice, st));
+            if (!owner_node.empty()) BHIP(b, hipMemcpyAsync(d_owner_node.p, owner_node.data(), (size_t)n_owner * 4, hipMemcpyHostToDevice, st));
         }
-        BHIP(b, hipMemcpyAsync(parent.p, b->parent.data(), b->parent.size() * 4, hipMemcpyHostToDevice, st));
-        BHIP(b, hipMemcpyAsync(depth.p, b->depth.data(), b->depth.size() * 4, hipMemcpyHostToDevice, st));
-        BHIP(b, hipMemcpyAsync(node_tid.p, b->node_tid.data(), b->node_tid.size() * 4, hipMemcpyHostToDevice, st));
+        if (!b->parent.empty()) {   // (id mode has no tree)
+            BHIP(b, hipMemcpyAsync(parent.p, b->parent.data(), b->parent.size() * 4, hipMemcpyHostToDevice, st));
+            BHIP(b, hipMemcpyAsync(depth.p, b->depth.data(), b->depth.size() * 4, hipMemcpyHostToDevice, st));
+        }
+        if (!b->node_tid.empty()) BHIP(b, hipMemcpyAsync(node_tid.p, b->node_tid.data(), b->node_tid.size() * 4, hipMemcpyHostToDevice, st));
         BHIP(b, hipStreamSynchronize(st));
         BHIP(b, hipHostMalloc((void**)&stage, chunk_alloc));
         BHIP(b, timer.init(st));
+        return LMAT_OK;
+    }
+
+    // id mode: the slice of every input with the pass's prefix as (k-mer, owner) pairs with the source flag set, on the host; cap minus their
+    // number is what the extraction of the pass may emit
+    void slice_inputs(u32 pass) {
+        slices.clear();
+        in_keys.clear();
+        in_vals.clear();
+        const int k = b->k;
+        for (size_t s = 0; s < b->inputs.size(); ++s) {
+            const auto& in = b->inputs[s];
+            const size_t lo = cursor[s];
+            size_t hi = in.kmers.size();
+            if (pb) hi = (size_t)(std::lower_bound(in.kmers.begin() + lo, in.kmers.end(), ((u64)pass + 1) << (2 * k - pb)) - in.kmers.begin());
+            cursor[s] = hi;
+            if (hi == lo) continue;
+            slices.push_back(Slice{s, lo, hi});
+            for (size_t i = lo; i < hi; ++i)
+                for (u64 e = in.off[i]; e < in.off[i + 1]; ++e) {
+                    const u32 ow = in_owner[s][e];
+                    if (packed) in_keys.push_back((((in.kmers[i] << ob) | ow) << 1) | 1ull);
+                    else { in_keys.push_back(in.kmers[i]); in_vals.push_back((ow << 1) | 1u); }
+                }
+        }
+        in_pairs = in_keys.size();   // <= cap: plan() sized cap by the largest slice
+    }
+
+    // ... behind the N extracted pairs
+    int append_inputs(u64 N) {
+        if (!in_pairs) return LMAT_OK;
+        BHIP(b, hipMemcpyAsync(keysA.as<u64>() + N, in_keys.data(), in_pairs * 8, hipMemcpyHostToDevice, st));
+        if (!packed) BHIP(b, hipMemcpyAsync(valsA.as<u32>() + N, in_vals.data(), in_pairs * 4, hipMemcpyHostToDevice, st));
+        BHIP(b, hipStreamSynchronize(st));
+        BHIP(b, timer.lap(b->mstats.upload_ms));
         return LMAT_OK;
     }
 
@@ -1412,10 +1614,11 @@ struct BuildRun {
             a.k = b->k;
             a.prefix_bits = pb;
             a.owner_bits = packed ? ob : -1;
+            a.flag_bits = fb;
             a.pass = pass;
             a.keys = keysA.as<u64>();
             a.vals = valsA.as<u32>();
-            a.cap = cap;
+            a.cap = cap - in_pairs;
             a.counters = counters.as<u64>();
             const u32 grid = (u32)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
             hipLaunchKernelGGL(extract_kernel, dim3(grid), dim3(64 * kWavesPerBlock), 0, st, a);
@@ -1434,14 +1637,15 @@ struct BuildRun {
         // ---- sort by (k-mer, owner)
         Sorted sorted;
         sorted.owner_bits = packed ? ob : -1;
+        sorted.flag_bits = fb;
         if (packed) {
-            BHIP(b, with_temp(temp, [&](void* t, size_t& tb) { return rocprim::radix_sort_keys(t, tb, keysA.as<u64>(), keysB.as<u64>(), N, 0, 2 * k + ob, st); }));
+            BHIP(b, with_temp(temp, [&](void* t, size_t& tb) { return rocprim::radix_sort_keys(t, tb, keysA.as<u64>(), keysB.as<u64>(), N, 0, 2 * k + ob + fb, st); }));
             sorted.keys = keysB.as<u64>();
             sorted.vals = nullptr;
         } else {
             BHIP(b, with_temp(temp, [&](void* t, size_t& tb) {   // by owner, then -- stable -- by k-mer: one storage for both
                 size_t tb1 = tb, tb2 = tb;
-                hipError_t e = rocprim::radix_sort_pairs(t, tb1, valsA.as<u32>(), valsB.as<u32>(), keysA.as<u64>(), keysB.as<u64>(), N, 0, ob, st);
+                hipError_t e = rocprim::radix_sort_pairs(t, tb1, valsA.as<u32>(), valsB.as<u32>(), keysA.as<u64>(), keysB.as<u64>(), N, 0, ob + fb, st);
                 if (e == hipSuccess) e = rocprim::radix_sort_pairs(t, tb2, keysB.as<u64>(), keysA.as<u64>(), valsB.as<u32>(), valsA.as<u32>(), N, 0, 2 * k, st);
                 tb = std::max(tb1, tb2);
                 return e;
@@ -1464,6 +1668,7 @@ struct BuildRun {
         BHIP(b, timer.lap(S.segment_ms));
         R = (u32)tot[1];
         S.distinct_kmers += R;
+        if (b->id_mode) return id_lists(sorted, N, R, off_buf);
 
         // ---- closure: count, then the shared tail.  cnt reuses the flag array, off a key buffer (both are R + 1 <= N + 1 long at most)
         ClosureArgs ca;
@@ -1498,6 +1703,57 @@ struct BuildRun {
         return LMAT_OK;
     }
 
+    // id mode, behind the segmentation: which runs hold a pair from text (while flag and pos still are the segmentation's), then the list stage
+    int id_lists(const Sorted& sorted, u64 N, u32 R, DevBuf*& off_buf) {
+        if (fb) {
+            BHIP(b, has_text.ensure((size_t)R * 4));
+            BHIP(b, hipMemsetAsync(has_text.p, 0, (size_t)R * 4, st));
+            hipLaunchKernelGGL(text_runs_kernel, dim3((u32)((N + 255) / 256)), dim3(256), 0, st, sorted, N, flag.as<u64>(), pos.as<u64>(), has_text.as<u32>());
+            BHIP(b, hipGetLastError());
+        }
+        IdListArgs ia;
+        memset(&ia, 0, sizeof(ia));
+        ia.R = R;
+        ia.run_start = run.as<u32>();
+        ia.d_owner = downer.as<u32>();
+        ia.id_of = node_tid.as<u32>();
+        ia.cnt = flag.as<u64>();
+        ia.counters = counters.as<u64>();
+        const u32 gridR = (u32)(((u64)R + 64 * kWavesPerBlock - 1) / (64 * kWavesPerBlock));
+        hipLaunchKernelGGL(idlist_kernel<false>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ia);
+        BHIP(b, hipGetLastError());
+        off_buf = packed ? &keysA : &keysB;
+        if ((u64)R + 1 > cap) BHIP(b, off_buf->ensure(((u64)R + 1) * 8));
+        const int rc = write_lists(b, st, "gene id list", R, flag.as<u64>(), off_buf->as<u64>(), counters.as<u64>(), hc, C_N, tids, lng, temp,
+                                   [&](const u64* d_off, u32* d_tids, const LongArgs&) {
+                                       ia.off = d_off;
+                                       ia.tids = d_tids;
+                                       hipLaunchKernelGGL(idlist_kernel<true>, dim3(gridR), dim3(64 * kWavesPerBlock), 0, st, ia);
+                                       return hipGetLastError();
+                                   });
+        if (rc) return rc;
+        hipLaunchKernelGGL(run_kmer_kernel, dim3((R + 255) / 256), dim3(256), 0, st, dk.as<u64>(), run.as<u32>(), R, pos.as<u64>());
+        BHIP(b, hipGetLastError());
+        BHIP(b, timer.lap(b->stats.closure_ms));
+        return LMAT_OK;
+    }
+
+    // id mode with inputs: the sources of every record of the pass -- the text (has_text) and every input whose slice holds the k-mer
+    int source_stats(u32 R, const std::vector<u64>& h_km) {
+        std::vector<u32> n_src(R);
+        BHIP(b, hipMemcpy(n_src.data(), has_text.p, (size_t)R * 4, hipMemcpyDeviceToHost));
+        for (const Slice& sl : slices) {
+            const auto& in = b->inputs[sl.input];
+            size_t j = 0;
+            for (size_t i = sl.lo; i < sl.hi; ++i) {   // both ascend, and every k-mer of an input is a record of the result
+                while (j < R && h_km[j] < in.kmers[i]) ++j;
+                if (j < R) n_src[j] += 1;
+            }
+        }
+        for (u32 r = 0; r < R; ++r) (n_src[r] > 1 ? b->mstats.records_merged : b->mstats.records_one_source) += 1;
+        return LMAT_OK;
+    }
+
     // the pass's records to the host: those without a known owner are left out (tax_histo.cpp:239-248)
     int fetch(u32 R, const DevBuf& off_buf) {
         const u64 entries = hc[C_ENTRIES];
@@ -1507,6 +1763,7 @@ struct BuildRun {
         BHIP(b, hipMemcpy(h_km.data(), pos.p, (size_t)R * 8, hipMemcpyDeviceToHost));
         BHIP(b, hipMemcpy(h_off.data(), off_buf.p, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost));
         if (entries) BHIP(b, hipMemcpy(b->tids.data() + t0, tids.p, entries * 4, hipMemcpyDeviceToHost));
+        if (fb) if (const int rc = source_stats(R, h_km)) return rc;
         for (u32 r = 0; r < R; ++r) {
             if (h_off[r + 1] == h_off[r]) continue;
             b->kmers.push_back(h_km[r]);
@@ -1524,7 +1781,15 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
     b->list_off.assign(1, 0);
     S.bases = b->bases;
     if (b->rec_start.size() > 0x7FFFFFFFull) return berr(b, LMAT_E_CAPACITY, "more than 2^31 FASTA records");
-    const bool merging = !b->inputs.empty();
+    const bool merging = !b->inputs.empty() && !b->id_mode, any_input = !b->inputs.empty();
+    if (b->id_mode) {   // the ids of this run's inputs, ascending: what the tree's node ids are to a tree-mode build
+        std::vector<u32>& ids = b->node_tid;
+        ids = b->rec_taxid;
+        for (const auto& in : b->inputs) ids.insert(ids.end(), in.nodes.begin(), in.nodes.end());
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        if (ids.size() > 0x7FFFFFFFull) return berr(b, LMAT_E_CAPACITY, "more than 2^31 distinct ids");
+    }
     b->node_counts.assign(b->node_tid.size(), 0);
     memset(&b->mstats, 0, sizeof(b->mstats));
     BuildRun r;
@@ -1532,7 +1797,7 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
     r.st = b->ctx->stream;
     r.T = b->text.size();
     r.n_rec = (u32)b->rec_start.size();
-    if ((r.T == 0 || r.n_rec == 0) && !merging) return LMAT_OK;
+    if ((r.T == 0 || r.n_rec == 0) && !any_input) return LMAT_OK;
     r.number_owners();
     if (const int rc = r.plan(pb_forced, pb_start)) return rc;
     const int pb = r.pb;
@@ -1543,17 +1808,27 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
     // the per-taxid histogram of the final lists, and the merge with the tax_histo inputs when there are any
     MergeState tail;
     if (const int rc = tail.begin(b, pb, r.tree(), &r.timer)) return rc;
+    if (r.fb) {
+        b->mstats.inputs = (uint32_t)b->inputs.size();
+        b->mstats.passes = 1u << pb;
+        for (const auto& in : b->inputs) { b->mstats.records_in += in.kmers.size(); b->mstats.entries_in += in.nodes.size(); }
+    }
 
     for (u32 pass = 0; pass < (1u << pb); ++pass) {
+        if (r.fb) r.slice_inputs(pass);
         if (const int rc = r.extract(pass)) return rc;
         if (r.hc[C_OVERFLOW]) {
             if (pb_forced < 0) { retry = true; return berr(b, LMAT_E_CAPACITY, "pass buffer too small"); }
             return berr(b, LMAT_E_CAPACITY, "prefix pass " + std::to_string(pass) + " of " + std::to_string(1u << pb) + " emits " + std::to_string(r.hc[C_CURSOR]) +
                                                " pairs, the device budget holds " + std::to_string(r.cap) + ": raise the budget or prefix_bits");
         }
-        const u64 N = r.hc[C_CURSOR];
+        u64 N = r.hc[C_CURSOR];
         if (pass == 0) S.windows = r.hc[C_WINDOWS];   // every pass sees every window; only the emitted pairs differ
         S.emitted_pairs += N;
+        if (r.fb) {
+            if (const int rc = r.append_inputs(N)) return rc;
+            N += r.in_pairs;
+        }
         if (N == 0) {
             if (merging) if (const int rc = tail.pass(pass, 0, nullptr, nullptr, nullptr, 0)) return rc;
             continue;
@@ -1587,12 +1862,14 @@ int run_build(lmat_build* b, int pb_forced, int pb_start, bool& retry) {
 extern "C" {
 
 int lmat_db_begin(lmat_ctx* ctx, int k, uint64_t n_kmers_hint, uint64_t table_bytes);
+int lmat_genedb_begin(lmat_ctx* ctx, int k, uint64_t n_kmers_hint, uint64_t table_bytes);
 int lmat_db_finalize(lmat_ctx* ctx);
 
 // The result goes through the ingest's own record parser as an in-memory stream of the file format, so the table is the one
 // lmat_db_begin / lmat_db_add_taxhisto / lmat_db_finalize build from the written file.
 int lmat_db_build_from_genomes(lmat_ctx* ctx, lmat_build* b, uint64_t table_bytes) {
     if (!ctx || !b) return LMAT_E_ARG;
+    if (b->id_mode) return lmat::set_err(ctx, LMAT_E_ARG, "an id-set builder holds gene ids: lmat_genedb_build_from_genes makes its table");
     if (!b->done) return lmat::set_err(ctx, LMAT_E_ARG, "lmat_build_run first");
     if (!ctx->tax.loaded) return lmat::set_err(ctx, LMAT_E_ARG, "load the taxonomy before the k-mer database");
     char* mem = nullptr;
@@ -1609,6 +1886,28 @@ int lmat_db_build_from_genomes(lmat_ctx* ctx, lmat_build* b, uint64_t table_byte
             const bool tax = ctx->ingest->err.compare(0, 3, "bad") == 0;
             rc = lmat::set_err(ctx, tax ? LMAT_E_TAXONOMY : LMAT_E_IO, ctx->ingest->err);
         }
+    }
+    free(mem);
+    if (rc == LMAT_OK) rc = lmat_db_finalize(ctx);
+    return rc;
+}
+
+// The same for an id-set builder and a gene context (lmat_genedb_begin): no taxonomy anywhere.
+int lmat_genedb_build_from_genes(lmat_ctx* ctx, lmat_build* b, uint64_t table_bytes) {
+    if (!ctx || !b) return LMAT_E_ARG;
+    if (!b->id_mode) return lmat::set_err(ctx, LMAT_E_ARG, "a tree-mode builder holds taxids: lmat_db_build_from_genomes makes its table");
+    if (!b->done) return lmat::set_err(ctx, LMAT_E_ARG, "lmat_build_run first");
+    char* mem = nullptr;
+    size_t mem_len = 0;
+    FILE* w = open_memstream(&mem, &mem_len);
+    if (!w) return lmat::set_err(ctx, LMAT_E_NOMEM, "open_memstream failed");
+    const bool ok = write_records(w, b);
+    if (fclose(w) != 0 || !ok || !mem) { free(mem); return lmat::set_err(ctx, LMAT_E_NOMEM, "out of memory for the record stream"); }
+    int rc = lmat_genedb_begin(ctx, b->k, 0, table_bytes);
+    if (rc == LMAT_OK) {
+        FILE* r = fmemopen(mem, mem_len, "rb");
+        if (!r) rc = lmat::set_err(ctx, LMAT_E_NOMEM, "fmemopen failed");
+        else if (!ctx->ingest->add_taxhisto_stream(r, "<built from genes>")) rc = lmat::set_err(ctx, LMAT_E_IO, ctx->ingest->err);
     }
     free(mem);
     if (rc == LMAT_OK) rc = lmat_db_finalize(ctx);

@@ -1,7 +1,7 @@
 // build_tax_histo -- genome FASTA + taxonomy tree -> the tax_histo binary read_label -d / make_db_image ingest, on the GPU.
 // One tool for the reference's kmerPrefixCounter (src/kmerPrefixCounter.cpp) + tax_histo (src/tax_histo.cpp) pair; the
 // closing stdout lines keep tax_histo's wording (tax_histo.cpp:297-313).  With -m existing tax_histo files are merged in (adding genomes to
-// a database), with -D a loaded database image is (needs -e / -w and, for a 16-bit database, -f: the files a context loads); -c writes the per-taxid k-mer counts of the result as countTaxidFrequency does (src/countTaxidFrequency.cpp:133-139).
+// a database), with -G a gene database is built (gene FASTA -> per k-mer the ids of the records that hold it; no tree), with -D a loaded database image is (needs -e / -w and, for a 16-bit database, -f: the files a context loads); -c writes the per-taxid k-mer counts of the result as countTaxidFrequency does (src/countTaxidFrequency.cpp:133-139).
 #include <unistd.h>
 #include <chrono>
 #include <cstdio>
@@ -18,6 +18,7 @@ static void usage() {
             " -l           - -i names a list of fasta files, one per line\n"
             " -k <int>     - kmer length (1..20)\n"
             " -t <string>  - tax tree data file\n"
+            " -G           - gene database: headers are '>' + gene id (1..4294967295), lists are the ids that hold the k-mer; takes no -t, no -D\n"
             " -o <string>  - output filename\n"
             " -b <float>   - device memory budget in GiB; optional; default: half of the free memory\n"
             " -m <string>  - existing tax_histo file to merge in (same -k); repeatable; optional\n"
@@ -37,10 +38,10 @@ int main(int argc, char* argv[]) {
     std::vector<std::string> merge_fns, image_fns;
     std::string depth_fn, rank_fn, map_fn;
     int k = 0, prefix_bits = -1;
-    bool is_list = false;
+    bool is_list = false, genes = false;
     double budget_gib = 0;
     int c;
-    while ((c = getopt(argc, argv, "i:lk:t:o:b:p:m:c:D:e:w:f:Vh")) != -1) {
+    while ((c = getopt(argc, argv, "i:lk:t:o:b:p:m:c:D:e:w:f:GVh")) != -1) {
         switch (c) {
             case 'i': input_fn = optarg; break;
             case 'l': is_list = true; break;
@@ -55,12 +56,15 @@ int main(int argc, char* argv[]) {
             case 'e': depth_fn = optarg; break;
             case 'w': rank_fn = optarg; break;
             case 'f': map_fn = optarg; break;
+            case 'G': genes = true; break;
             case 'V': printf("build_tax_histo (lmat_hip) 1\n"); return 0;
             default: usage(); return c == 'h' ? 0 : 255;
         }
     }
+    if (genes && !image_fns.empty()) { fprintf(stderr, "-D is not available with -G: device images hold taxonomy databases; merge gene databases as files (-m)\n"); return 255; }
+    if (genes && !tree_fn.empty()) { fprintf(stderr, "-G takes no taxonomy tree (-t)\n"); usage(); return 255; }
     if (!image_fns.empty() && depth_fn.empty()) { fprintf(stderr, "-D needs the taxonomy files of the image: -e <depth> -w <rank> [-f <map>]\n"); usage(); return 255; }
-    if ((input_fn.empty() && merge_fns.empty() && image_fns.empty()) || tree_fn.empty() || out_fn.empty() || k == 0) { usage(); return 255; }
+    if ((input_fn.empty() && merge_fns.empty() && image_fns.empty()) || (tree_fn.empty() && !genes) || out_fn.empty() || k == 0) { usage(); return 255; }
     std::vector<std::string> fastas;
     if (input_fn.empty()) {
     } else if (is_list) {
@@ -72,9 +76,9 @@ int main(int argc, char* argv[]) {
 
     lmat_ctx* ctx = nullptr;
     if (lmat_ctx_create(0, nullptr, &ctx) != LMAT_OK) { fprintf(stderr, "ERROR! no usable HIP device (the engine has no CPU path)\n"); return 1; }
-    printf("info: starting tax tree load from filename: %s\n", tree_fn.c_str());
+    if (!genes) printf("info: starting tax tree load from filename: %s\n", tree_fn.c_str());
     lmat_build* b = nullptr;
-    int rc = lmat_build_create(ctx, k, tree_fn.c_str(), &b);
+    int rc = genes ? lmat_genebuild_create(ctx, k, &b) : lmat_build_create(ctx, k, tree_fn.c_str(), &b);
     if (rc != LMAT_OK) { fprintf(stderr, "ERROR! %s\n", lmat_last_error(ctx)); lmat_ctx_destroy(ctx); return 1; }
     auto fail = [&](const char* what) {
         fprintf(stderr, "ERROR! %s: %s\n", what, lmat_build_error(b));
