@@ -551,6 +551,14 @@ int lmat_debug_decide(lmat_ctx* ctx, const uint32_t* tids, const float* scores, 
  * results[i]: status, match_type, cand_kmer_cnt, log_avg, stdev, call_tid, call_score. */
 int lmat_debug_decide_counts(lmat_ctx* ctx, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand,
                              uint64_t n, int on_the_wave, lmat_read_result* results);
+/* k4_wave on tables shaped as the closure leaves a read with ONE eligible id: the first kept[i] slots of table i are the ids the
+ * lists kept, eligible[i] is the slot among them whose ancestors -- registered by the closure, with its count -- fill the slots
+ * behind (kept[i] = 0: nothing is said about table i).  Such a table may be decided in closed form: took[i] = 1
+ * where it was, 0 where k4_wave's general code decided or declined it (status 255, as above).  with_cands != 0 attaches a
+ * candidate buffer as -p does: results[i].n_cand / cand_off are then set, and no table is taken.  LMAT_K4_CHAIN=0 takes none. */
+int lmat_debug_decide_chain(lmat_ctx* ctx, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand,
+                            const uint32_t* kept, const uint32_t* eligible, uint64_t n, int with_cands, lmat_read_result* results,
+                            uint8_t* took);
 
 /* ---- measurement aid ---------------------------------------------------------
  * Random 64-byte bucket gather over the loaded table with the probe kernel's access shape;

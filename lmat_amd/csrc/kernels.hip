@@ -1116,10 +1116,111 @@ __device__ __forceinline__ uint64_t bal(bool b) { return __builtin_amdgcn_ballot
 // The vector pipe is what the classify kernel runs out of, so this step is written for few VECTOR instructions: per-slot
 // loops read their operands as LDS broadcasts, four per load (a v_readlane is a vector instruction, a ds_read is not),
 // wave-uniform integers and lane masks stay on the scalar unit, and nothing branches per lane.
+// the record and the tallies of a decided read (proc_line :1241-1268), by lane 0
+__device__ __forceinline__ void k4_wave_record(CArgsK4* Ap, int lane, GAS uint64_t* out, const lmat_read_result& res, uint32_t call_idx) {
+    if (lane == 0) {
+        GAS unsigned long long* tally_count = (GAS unsigned long long*)Ap->counts;
+        GAS double* tally_score = (GAS double*)(tally_count + Ap->tb.n_ids);
+        GAS unsigned long long* tally_nomatch = (GAS unsigned long long*)(tally_score + Ap->tb.n_ids);
+        store_result(out, res);
+        if (res.status != LMAT_ST_PHIX && res.match_type == LMAT_MT_NOMATCH) {
+            G_ADD(&tally_nomatch[1], 1ull);
+        } else if (res.call_score >= Ap->prm.min_score) {
+            G_ADD(&tally_count[call_idx], 1ull);
+            G_ADD(&tally_score[call_idx], (double)res.call_score);
+        } else if (res.call_score < Ap->prm.min_score) {
+            G_ADD(&tally_nomatch[2], 1ull);
+        }
+    }
+}
+// One lineage, decided in closed form.  `chain` = eligible slot | kept slots << 8 | 1 << 16 comes from a closure
+// that found ONE eligible id (slot sx0) and registered every one of its ancestors itself: slots 0 .. kept-1 are the ids the lists
+// kept, the slots behind them the ancestors of sx0 ("the chain"), each with sx0's count c0.  When every other kept id has a count
+// below c0 and an Euler interval disjoint from sx0's, and the chain ends at depth 0, findReadLabelVer2 (:284-419) collapses:
+//   * sorted by (count, depth) the array ends ... others | chain by rising depth | sx0: the lineage loop (:295-325) takes sx0 and
+//     the whole chain (each an ancestor of all before it) and stops at the best other id, which is unrelated to sx0
+//     (addToCandLineage :225-262 meets sx0 first); lowest = sx0, highest = the chain's end at depth 0: nothing is added (:326-343);
+//   * every lineage score is s0 = c0 / cand, so cmpCompLineage (:264-282) sees ONE difference d = s0 - s_j per other id j, and meets
+//     it first at the entry sx0, never an ancestor of j: d > diff_thresh ends the whole scan with no mark from j; d <= diff_thresh
+//     marks every entry that is no ancestor of j.  Scores rise with the counts (correctly rounded quotients over one cand), so d
+//     does not fall along the scan: an id with d <= diff_thresh is never behind one that ended the scan, whatever std::sort made of
+//     equal keys.  The marked entries are those deeper than the LCA of sx0 and some j with d <= diff_thresh -- the one compare the
+//     reference marks by; its other compare decides nothing more;
+//   * nothing marked: Direct, (sx0, s0).  Else the deepest chain entry that is an ancestor of every such j: Multi with max_val = s0
+//     (the chain is registered, its scores are all s0: never Partial, :398-407); none: LCA error.
+// The statistics (:803-880) are the general path's own, operand for operand, without the rank count.  No sort, no all-pairs pass,
+// no ds_permute, no lineage loop.  Every test is wave-uniform; a table that fails one is the general path's.
+__device__ __forceinline__ bool k4_wave_chain(CArgsK4* Ap, int lane, uint32_t nT, uint32_t cand, const u32x4 fz, uint32_t my_cnt,
+                                              uint32_t my_id, uint32_t dep, uint32_t fl, uint32_t chain, uint32_t* xch, GAS uint64_t* out,
+                                              int valid_kmers, uint32_t len, int bin_sel) {
+    const uint32_t sx0 = chain & 63u, nK = (chain >> 8) & 0x7Fu;
+    if (nK - 1u >= nT - 1u || sx0 >= nK) return false;   // 1 <= kept < nT (a chain behind them), the eligible slot among the kept
+    const uint64_t am = below_mask_1_64((int)nT), KEPT = below_mask_1_64((int)nK), CH = am & ~KEPT, OTH = KEPT & ~(1ull << sx0);
+    const uint32_t ti = fz.z & 0xFFFFu, oi = fz.z >> 16;
+    const uint32_t c0 = rl(my_cnt, (int)sx0), riv = rl(fz.z, (int)sx0);
+    const uint32_t rt = riv & 0xFFFFu, ro = riv >> 16;
+    const uint32_t badfl = (uint32_t)kFlagPlasmid | (Ap->prm.screen_phix ? (uint32_t)kFlagPhiX : 0u);
+    // counts: the others below c0 (an equal count at an equal depth is a tie std::sort decides), the chain at c0
+    if ((~bal(my_cnt < c0) & OTH) | (~bal(my_cnt == c0) & CH)) return false;
+    // intervals: the others neither above nor below sx0, the chain above it (depths grow along every branch: k4_static_of)
+    if ((~(bal(oi < rt) | bal(ro < ti)) & OTH) | (~(bal(ti < rt) & bal(ro <= oi)) & CH)) return false;
+    // the chain reaches depth 0 (else :326-343 adds unregistered ancestors); no plasmid (:301-304), no screened PhiX id (:841-848)
+    if (!(bal(dep == 0u) & CH) || bal((fl & badfl) != 0)) return false;
+    float* xs = (float*)xch;          // [64] scores by slot, [64] squared deviations: as k4_wave lays them out
+    float* xv = (float*)(xch + 256);
+    const float sc = div_small_ints((float)my_cnt, (float)cand);
+    xs[lane] = sc;
+    WSYNC();
+    float log_sum = 0.0f;
+    for (uint32_t t = 0; t < nT; t += 4) {
+        const u32x4 q = *(const u32x4*)((const uint32_t*)xs + t);
+        log_sum += __uint_as_float(q.x); log_sum += __uint_as_float(q.y); log_sum += __uint_as_float(q.z); log_sum += __uint_as_float(q.w);
+    }
+    const uint32_t pos_sig_hits = (uint32_t)popc64(bal(my_cnt > 0));
+    const uint32_t use_sig_hits = pos_sig_hits > 3 ? pos_sig_hits : nT;
+    const float log_avg = div_small_ints(log_sum, (float)use_sig_hits);
+    const float dv = log_avg - sc;
+    xv[lane] = (uint32_t)lane < nT && (pos_sig_hits > 3 ? my_cnt > 0 : true) ? dv * dv : 0.0f;
+    WSYNC();
+    float log_std = 0.0f;
+    for (uint32_t t = 0; t < nT; t += 4) {
+        const f32x4 q = *(const f32x4*)(xv + t);
+        log_std += q.x; log_std += q.y; log_std += q.z; log_std += q.w;
+    }
+    const float stdev1 = use_sig_hits > 1 ? sqrtf(div_small_ints(log_std, (float)(use_sig_hits - 1))) : 0.0f;
+    const float diff_thresh = stdev1 * Ap->prm.sdiff;
+    const float s0 = __uint_as_float(rl(__float_as_uint(sc), (int)sx0));
+    const float d = s0 - sc;
+    uint64_t close = bal(d <= diff_thresh) & OTH;
+    uint8_t match = LMAT_MT_DIRECT;
+    uint32_t call_tid = rl(my_id, (int)sx0);
+    float call_score = s0;
+    if (close) {
+        uint64_t good = CH;   // chain entries that are ancestors of every close id so far
+        do {
+            const uint32_t ivj = rl(fz.z, __builtin_ctzll(close));
+            close &= close - 1;
+            good &= bal(ti < (ivj & 0xFFFFu)) & bal((ivj >> 16) <= oi);
+        } while (close && good);
+        if (!good) {
+            match = LMAT_MT_LCA_ERROR; call_tid = 0; call_score = 0;
+        } else {  // the deepest of nested ancestors has the largest tin
+            const uint32_t k = wave_max_u32(lane_bit(good) ? (ti << 6) | (uint32_t)lane : 0u);
+            match = LMAT_MT_MULTI; call_tid = rl(my_id, (int)(k & 63u));
+        }
+    }
+    lmat_read_result res;
+    res.status = LMAT_ST_CALL; res.match_type = match; res.cand_kmer_cnt = (uint16_t)cand; res.valid_kmers = valid_kmers;
+    res.read_len = (int)len; res.log_avg = log_avg; res.stdev = stdev1; res.cand_off = 0; res.n_cand = 0; res.bin_sel = bin_sel;
+    res.call_tid = call_tid ? ((const GAS uint32_t*)Ap->tb.tid32)[call_tid] : 0u;
+    res.call_score = call_score;
+    k4_wave_record(Ap, lane, out, res, call_tid);
+    return true;
+}
 template <int THM, bool PLAIN = false>   // PLAIN: see classify_one
 __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint32_t cand, const u32x4 fz, uint32_t my_cnt,
                                         uint32_t my_id, const unsigned int* hent, uint32_t* xch, GAS uint64_t* out,
-                                        int valid_kmers, uint32_t len, int bin_sel) {
+                                        int valid_kmers, uint32_t len, int bin_sel, uint32_t chain = 0, uint32_t* took_chain = nullptr) {
     const float hbias = PLAIN ? 0.0f : Ap->prm.hbias, sdiff = Ap->prm.sdiff;
     const int screen_phix = Ap->prm.screen_phix;
     // what does not depend on the read -- no null model, no debug stop outside 30 .. 34, depths that grow along every branch, candidates
@@ -1144,6 +1245,15 @@ __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint
     const bool act = (uint32_t)lane < nT;
     const uint32_t dep = act ? (fz.w & 0xFFFFu) : 0u, fl = act ? (fz.w >> 16) : 0u;
     if (bal(my_cnt > cand) | bal(dep > 0x7FFFu) | (hbias != 0.0f ? bal((fl & kFlagHuman) != 0) : 0ull)) return false;  // (a bias of 0 adds 0 * stdev: nothing)
+    // one eligible id and its chain (the closure says so): the closed form, where the launch allows it (k4_static_of, bit 2: no -p,
+    // no debug stop, LMAT_K4_CHAIN) and the table has its shape
+    if (LMAT_ABLATE && lane == 0) { G_ADD((GAS uint32_t*)Ap->cursor + kCurChainSeen, 1u); if (chain) G_ADD((GAS uint32_t*)Ap->cursor + kCurChainLone, 1u); }
+    if (chain && (PLAIN || (Ap->prm.k4_static & 4)) &&
+        k4_wave_chain(Ap, lane, nT, cand, fz, my_cnt, my_id, dep, fl, chain, xch, out, valid_kmers, len, bin_sel)) {
+        if (LMAT_ABLATE && lane == 0) G_ADD((GAS uint32_t*)Ap->cursor + kCurChainTaken, 1u);
+        if (took_chain) *took_chain = 1u;
+        return true;
+    }
     float* xs = (float*)xch;      // [64] scores by slot (stay: a registered ancestor's score is read from here)
     uint32_t* xk = xch + 64;      // [64] sort keys by array position; later the taxid of every sorted position
     uint32_t* xx = xch + 128;     // [128] exchange buffer of a partition step; later the Euler intervals by sorted position
@@ -1445,20 +1555,7 @@ __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint
             if (co) res.n_cand = nT;
         }
     }
-    if (lane == 0) {
-        GAS unsigned long long* tally_count = (GAS unsigned long long*)Ap->counts;
-        GAS double* tally_score = (GAS double*)(tally_count + Ap->tb.n_ids);
-        GAS unsigned long long* tally_nomatch = (GAS unsigned long long*)(tally_score + Ap->tb.n_ids);
-        store_result(out, res);
-        if (res.status != LMAT_ST_PHIX && res.match_type == LMAT_MT_NOMATCH) {  // tallies, proc_line :1241-1268
-            G_ADD(&tally_nomatch[1], 1ull);
-        } else if (res.call_score >= Ap->prm.min_score) {
-            G_ADD(&tally_count[call_idx], 1ull);
-            G_ADD(&tally_score[call_idx], (double)res.call_score);
-        } else if (res.call_score < Ap->prm.min_score) {
-            G_ADD(&tally_nomatch[2], 1ull);
-        }
-    }
+    k4_wave_record(Ap, lane, out, res, call_idx);
     return true;
 #undef PDEP
 #undef PTID_AT
@@ -3009,6 +3106,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     WSYNC();
     STOP_AT(5, nT);
     RELANE();
+    uint32_t chain = 0;  // what the closure tells the decision step (k4_wave_chain): eligible slot | kept slots << 8 | 1 << 16, when `lone` held
     // representative strain per species (read_label.cpp:1144-1177): max leaf count, ties -> smallest taxid
     // (-s: the whole post pass :1143-1204 is skipped; the list records already hold the lineages)
     if constexpr (INK4) {
@@ -3226,6 +3324,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         if (lone) {
             const uint32_t c0 = cnt[sx0];
             if ((uint32_t)lane >= nT_p1 && (uint32_t)lane < nT) cnt[lane] = (uint16_t)c0;
+            chain = 0x10000u | (nT_p1 << 8) | (uint32_t)sx0;
             WSYNC();
         } else if (!overflow && W > 0) {
             const bool sl_act = (uint32_t)lane < nT;
@@ -3356,7 +3455,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         if constexpr (!INK4) {
             if (!rows) {
                 const uint32_t my_cnt = (uint32_t)lane < nT ? (uint32_t)cnt[lane] : 0u, my_id = (uint32_t)lane < nT ? (uint32_t)reg[lane] : 0u;
-                if (k4_wave<THM, PLAIN>(Ap, lane, nT, cand, fz, my_cnt, my_id, hent, (uint32_t*)(lds + L::OFF_R3), out, valid_kmers, len, bin_sel)) return;
+                if (k4_wave<THM, PLAIN>(Ap, lane, nT, cand, fz, my_cnt, my_id, hent, (uint32_t*)(lds + L::OFF_R3), out, valid_kmers, len, bin_sel, chain)) return;
             }
         }
         GAS uint32_t* krec = (GAS uint32_t*)A.k4buf + (r - A.result_base) * kK4RecWords;
@@ -3816,8 +3915,11 @@ __global__ __launch_bounds__(64) void k4_debug_counts_kernel(ClassifyArgs A, con
 // set up as classify_one leaves a read: lane s = registration slot s with the id's fact record in its registers, the ids in the
 // wave's taxid hash.  A table k4_wave declines (its preconditions, the heapsort turn of introsort, a lineage beyond 64 lanes,
 // two lineage entries of one depth) comes back with status 255: the general path's job.
+// `shape` (optional): per table what the closure would tell k4_wave -- eligible slot | kept slots << 8 | 1 << 16, or 0 --; `took` then
+// receives a byte per table: 1 where the closed form (k4_wave_chain) decided it.
 __global__ __launch_bounds__(64) void k4_wave_debug_kernel(ClassifyArgs A, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ cnts,
-                                                           const uint64_t* __restrict__ off, const uint32_t* __restrict__ cands, uint64_t n) {
+                                                           const uint64_t* __restrict__ off, const uint32_t* __restrict__ cands, uint64_t n,
+                                                           const uint32_t* __restrict__ shape, uint8_t* __restrict__ took) {
     constexpr int THM = 255;
     __shared__ __align__(16) unsigned int hent[THM + 1];
     __shared__ __align__(16) uint32_t xch[384 + 64];
@@ -3826,6 +3928,7 @@ __global__ __launch_bounds__(64) void k4_wave_debug_kernel(ClassifyArgs A, const
         const uint32_t nT = (uint32_t)(off[i + 1] - off[i]);
         GAS uint64_t* out = (GAS uint64_t*)(A.results + i);
         bool done = false;
+        uint32_t took_chain = 0;
         if (nT >= 1 && nT <= 64) {
             for (int h = lane; h <= THM; h += 64) hent[h] = 0;
             WSYNC();
@@ -3838,9 +3941,11 @@ __global__ __launch_bounds__(64) void k4_wave_debug_kernel(ClassifyArgs A, const
                 hent[h] = my_id | ((uint32_t)lane << 16);
             }
             WSYNC();
-            done = k4_wave<THM>((CArgsK4*)__builtin_amdgcn_kernarg_segment_ptr(), lane, nT, cands[i], fz, my_cnt, my_id, hent, xch, out, 0, 0u, 0);
+            done = k4_wave<THM>((CArgsK4*)__builtin_amdgcn_kernarg_segment_ptr(), lane, nT, cands[i], fz, my_cnt, my_id, hent, xch, out, 0, 0u, 0,
+                                shape ? (uint32_t)__builtin_amdgcn_readfirstlane((int)shape[i]) : 0u, &took_chain);
             WSYNC();
         }
+        if (took && lane == 0) took[i] = (uint8_t)took_chain;
         if (!done && lane == 0) {
             lmat_read_result res;
             res.status = 255; res.match_type = LMAT_MT_NOMATCH; res.cand_kmer_cnt = 0; res.valid_kmers = 0; res.read_len = 0; res.log_avg = 0;
@@ -4102,13 +4207,16 @@ void launch_k4_end(const ClassifyArgs& a, hipStream_t join_stream, hipStream_t s
     hipEventRecord(done, join_stream);
 }
 
-// Which decision paths the launch allows (bit 0: k4_wave, bit 1: k4_row_kernel), from what does not vary with the read.
+// Which decision paths the launch allows (bit 0: k4_wave, bit 1: k4_row_kernel, bit 2: k4_wave's closed form for one lineage,
+// k4_wave_chain), from what does not vary with the read.  The closed form leaves the candidate pairs of -p, which want every
+// candidate in sorted order, to the general code of k4_wave; LMAT_K4_CHAIN=0 turns it off.
 static int k4_static_of(const ClassifyArgs& a) {
     const int stop = a.prm.stop_after;
     const bool base = !a.nm.active && a.tb.depth_consistent && !(a.cands && !a.prm.prn_all);
     const bool wave = base && (stop == 0 || (stop >= 30 && stop <= 34));
     const bool rows = base && a.prm.k4_row && stop == 0;
-    return (wave ? 1 : 0) | (rows ? 2 : 0);
+    const bool chain = wave && stop == 0 && !a.cands && a.prm.k4_chain;
+    return (wave ? 1 : 0) | (rows ? 2 : 0) | (chain ? 4 : 0);
 }
 // The plain run (classify_one's PLAIN): every launch-wide value the variant has as a literal, checked here.  What stays a run-time
 // scalar in it -- the bucket width in its three forms, sdiff, the k-mer and score thresholds, the PhiX screen -- is not asked
@@ -4116,7 +4224,7 @@ static int k4_static_of(const ClassifyArgs& a) {
 static bool plain_launch(const ClassifyArgs& a, int k4_static) {
     static const bool on = !LMAT_ABLATE && (!getenv("LMAT_PLAIN") || atoi(getenv("LMAT_PLAIN")) != 0);
     return on && a.tb.k == 20 && a.tb.cpt.nb && a.tb.cpt.m == 17 && a.tb.cpt.lowbits == 2 && !a.tb.wide && !a.nm.active && !a.rand_max &&
-           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 1 && !a.cands && a.prm.hbias == 0.0f &&
+           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 5 && !a.cands && a.prm.hbias == 0.0f &&
            a.p_min == 0 && a.p_max == 0xFFFFFFFFu && !a.index && !a.count_ptr && a.tail_lpr == 4;
 }
 // launches of <160, 64, kFastE> on a compact 16-bit table without -s (the class PLAIN is a variant of) by kernel, per device: [0] the
@@ -4172,13 +4280,13 @@ void launch_k4_debug(const ClassifyArgs& a, const uint32_t* idx, const float* sc
 }
 
 void launch_k4_debug_counts(const ClassifyArgs& a, const uint32_t* idx, const uint32_t* cnts, const uint64_t* off, const uint32_t* cands, uint64_t n,
-                            bool on_the_wave, hipStream_t stream) {
+                            bool on_the_wave, hipStream_t stream, const uint32_t* shape, uint8_t* took) {
     if (!n) return;
     if (on_the_wave) {
         const uint64_t g = n < 256 * 32 ? n : 256 * 32;
         ClassifyArgs b = a;
         b.prm.k4_static = k4_static_of(b);
-        k4_wave_debug_kernel<<<dim3((unsigned)g), dim3(64), 0, stream>>>(b, idx, cnts, off, cands, n);
+        k4_wave_debug_kernel<<<dim3((unsigned)g), dim3(64), 0, stream>>>(b, idx, cnts, off, cands, n, shape, took);
     } else k4_debug_counts_kernel<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream>>>(a, idx, cnts, off, cands, n);
 }
 

@@ -73,7 +73,10 @@ enum CursorWord {
     kCurK4Mid = 8,      // up to 32 taxids,
     kCurK4Row = 9,      // up to 16 taxids, decided by rows (LMAT_K4_ROW);
     kCurK4Bail = 6,     // reads a K4 kernel could not hold after all
-    kCurBatchErr = 15,  // error flags of a batch that keeps its own (the streamed boundary) instead of the sticky word
+    kCurChainSeen = 11, // ablation builds only (-DLMAT_ABLATE=1): reads that met k4_wave's entry conditions,
+    kCurChainLone = 12, // ... of them those whose closure found one eligible id and registered its whole chain,
+    kCurChainTaken = 13,// ... of them those the closed form decided (k4_wave_chain)
+    kCurBatchErr = 15, // error flags of a batch that keeps its own (the streamed boundary) instead of the sticky word
 };
 
 enum { kErrTidOverflow = 1, kErrReadTooLong = 2, kErrCandOverflow = 4, kErrLineageTrunc = 8, kErrNoNullModel = 16 };
@@ -104,8 +107,9 @@ void launch_k4_end(const ClassifyArgs& a, hipStream_t join_stream, hipStream_t s
                    hipEvent_t joined2, hipEvent_t joined3, hipEvent_t joined_small, hipEvent_t done);
 void launch_k4_debug(const ClassifyArgs& a, const uint32_t* idx, const float* scores, const uint64_t* off, const float* stdevs, uint64_t n,
                      hipStream_t stream);
+// shape / took (on the wave only, may be null): per table what the closure would tell k4_wave, and whether its closed form decided the table
 void launch_k4_debug_counts(const ClassifyArgs& a, const uint32_t* idx, const uint32_t* cnts, const uint64_t* off, const uint32_t* cands, uint64_t n,
-                            bool on_the_wave, hipStream_t stream);
+                            bool on_the_wave, hipStream_t stream, const uint32_t* shape = nullptr, uint8_t* took = nullptr);
 // launches of the 160-k-mer fast class (compact table, 16-bit ids, no -s) on `device` so far, by kernel: out[0] the generic instantiation, out[1] the PLAIN variant
 void classify_variant_launches(int device, uint64_t out[2]);
 int classify_max_read_len();

@@ -98,6 +98,9 @@ static KernelParams kparams(const lmat_params& p) {
     // every wave-uniform value of k4_wave into vector work, ~1400 instructions per wave of four reads, no cheaper per read than the
     // ~390 of k4_wave -- and the step takes 7.5 ms instead of 7.1.  Off by default; kept as the measured alternative.
     k.k4_row = getenv("LMAT_K4_ROW") && atoi(getenv("LMAT_K4_ROW")) != 0;
+    // LMAT_K4_CHAIN=0: reads of one lineage are decided by the general code of k4_wave, not by its closed form (k4_wave_chain).  The
+    // plain-run variant has the closed form compiled in, so such a run takes the generic kernel: the off arm of the tests.
+    k.k4_chain = !(getenv("LMAT_K4_CHAIN") && atoi(getenv("LMAT_K4_CHAIN")) == 0);
     k.k4_static = 0;
     return k;
 }
@@ -1929,15 +1932,15 @@ int lmat_debug_decide(lmat_ctx* c, const uint32_t* tids, const float* scores, co
 
 // The decision step on (taxid, count) tables: on_the_wave = 1 runs k4_wave -- the code the benchmarked path runs on the classify
 // wave --, 0 the general path (k4_part1 / k4_part2, the one lmat_debug_decide pins to the reference's printed records).
-int lmat_debug_decide_counts(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand, uint64_t n,
-                             int on_the_wave, lmat_read_result* results) {
-    if (!c || !tids || !counts || !off || !cand || !results) return LMAT_E_ARG;
+// (shape / with_cands / took: lmat_debug_decide_chain's additions, below)
+static int debug_decide_counts(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand, uint64_t n,
+                               int on_the_wave, const std::vector<uint32_t>* shape, int with_cands, lmat_read_result* results, uint8_t* took) {
     std::vector<uint32_t> idx;
     int rc = debug_tables(c, tids, counts, n ? off[n] : 0, idx);
     if (rc || !n) return rc;
     hipSetDevice(c->device);
     const uint64_t total = off[n];
-    DevBuf d_idx, d_cn, d_cd, d_off, d_res, d_tally;
+    DevBuf d_idx, d_cn, d_cd, d_off, d_res, d_tally, d_shape, d_took, d_cands;
     HIPCHK(c, d_tally.ensure(c->counts_bytes));   // k4_wave tallies its calls: into a buffer nobody reads
     HIPCHK(c, hipMemsetAsync(d_tally.p, 0, c->counts_bytes, c->stream));
     if ((rc = debug_put(c, d_idx, idx.data(), total * 4)) || (rc = debug_put(c, d_cn, counts, total * 4)) ||
@@ -1958,8 +1961,36 @@ int lmat_debug_decide_counts(lmat_ctx* c, const uint32_t* tids, const uint32_t* 
     auto it = c->tax.index_of.find(32630);
     a.phix_call_idx = it == c->tax.index_of.end() ? 0 : it->second;
     a.nm = NullModelDev();
-    launch_k4_debug_counts(a, d_idx.as<uint32_t>(), d_cn.as<uint32_t>(), d_off.as<uint64_t>(), d_cd.as<uint32_t>(), n, on_the_wave != 0, c->stream);
+    if (shape && (rc = debug_put(c, d_shape, shape->data(), n * 4))) return rc;
+    if (took) HIPCHK(c, d_took.ensure(n));
+    if (with_cands) {  // -p: room for every table's pairs, straight off the bump cursor
+        HIPCHK(c, d_cands.ensure(total * sizeof(lmat_cand)));
+        a.cands = d_cands.as<lmat_cand>();
+        a.cand_cap = total;
+        a.prm.prn_all = 1;
+    }
+    launch_k4_debug_counts(a, d_idx.as<uint32_t>(), d_cn.as<uint32_t>(), d_off.as<uint64_t>(), d_cd.as<uint32_t>(), n, on_the_wave != 0, c->stream,
+                           shape ? d_shape.as<uint32_t>() : nullptr, took ? d_took.as<uint8_t>() : nullptr);
+    if (took) HIPCHK(c, hipMemcpyAsync(took, d_took.p, n, hipMemcpyDeviceToHost, c->stream));
     return debug_fetch(c, d_res, n, results);
+}
+int lmat_debug_decide_counts(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand, uint64_t n,
+                             int on_the_wave, lmat_read_result* results) {
+    if (!c || !tids || !counts || !off || !cand || !results) return LMAT_E_ARG;
+    return debug_decide_counts(c, tids, counts, off, cand, n, on_the_wave, nullptr, 0, results, nullptr);
+}
+// k4_wave on tables as a closure with one eligible id leaves them: the first kept[i] slots of table i are the ids the lists kept,
+// eligible[i] is the slot among them whose ancestors fill the rest (kept[i] = 0: no such table).  took[i] = 1 where the closed form
+// (kernels.hip k4_wave_chain) decided the table; with_cands attaches a candidate buffer, as -p does.
+int lmat_debug_decide_chain(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand,
+                            const uint32_t* kept, const uint32_t* eligible, uint64_t n, int with_cands, lmat_read_result* results, uint8_t* took) {
+    if (!c || !tids || !counts || !off || !cand || !kept || !eligible || !results || !took) return LMAT_E_ARG;
+    std::vector<uint32_t> shape(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (kept[i] > 64u || (kept[i] && eligible[i] >= kept[i])) return set_err(c, LMAT_E_ARG, "kept slots above 64, or an eligible slot that is not among them");
+        shape[i] = kept[i] ? (0x10000u | (kept[i] << 8) | eligible[i]) : 0u;
+    }
+    return debug_decide_counts(c, tids, counts, off, cand, n, 1, &shape, with_cands, results, took);
 }
 
 // Measurement hook: the per-launch counter block of the most recent launch (after lmat_sync), words as kernels.hpp's CursorWord
