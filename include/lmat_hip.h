@@ -224,6 +224,10 @@ int lmat_reads_synth(lmat_ctx* ctx, uint64_t n, const uint32_t* lengths, uint32_
                      lmat_reads** out);
 int lmat_reads_download_ascii(lmat_ctx* ctx, const lmat_reads* r, uint64_t first, uint64_t count, uint8_t* bases,
                               uint64_t* off);
+/* Test hook: the packed records of reads first .. first + count as they lie on the device -- rec_off[count + 1] word
+ * offsets counted from the first of them, and (words != NULL) those rec_off[count] words.  A plain device-to-host copy. */
+int lmat_debug_reads_words(lmat_ctx* ctx, const lmat_reads* reads, uint64_t first, uint64_t count, uint32_t* words,
+                           uint64_t* rec_off);
 uint64_t lmat_reads_count(const lmat_reads* r);
 uint64_t lmat_reads_device_bytes(const lmat_reads* r);
 void lmat_reads_free(lmat_ctx* ctx, lmat_reads* r);
@@ -266,8 +270,9 @@ int lmat_results_fetch(lmat_ctx* ctx, uint64_t first, uint64_t count, lmat_read_
  *   next     -> waits for the OLDEST submitted batch; pointers into its pinned result buffers (cands in the order of
  *               lmat_read_result.cand_off), valid until lmat_stream_release; returns 1 when nothing is in flight
  *   release  -> the batch handed out by lmat_stream_next is consumed, its slot is free again
- * cands_per_read = 0: calls only; otherwise the slot holds cands_per_read x max_reads candidate pairs and grows itself
- * when a batch needs more.  Tallies accumulate in the context as with lmat_classify.  One thread drives a stream. */
+ * cands_per_read = 0: calls only; otherwise the slot holds cands_per_read x max_reads + 1024 x 2048 candidate pairs and
+ * grows itself when a batch needs more: fourfold, running the batch again inside lmat_stream_next without tallying it
+ * again.  Tallies accumulate in the context as with lmat_classify.  One thread drives a stream. */
 int lmat_stream_create(lmat_ctx* ctx, uint64_t max_reads, uint64_t max_bases, uint32_t cands_per_read, int n_slots,
                        lmat_stream** out);
 int lmat_stream_acquire(lmat_stream* st, uint8_t** bases, uint64_t** off);
@@ -281,8 +286,17 @@ int lmat_host_alloc(uint64_t bytes, void** out);
 void lmat_host_free(void* p);
 int lmat_stream_next(lmat_stream* st, const lmat_read_result** results, const lmat_cand** cands, uint64_t* n_reads,
                      uint64_t* n_cands, uint64_t* tag);
+/* Also drops a batch whose error lmat_stream_next has just reported (the error comes back for as long as the batch is
+ * asked for; the batches queued behind it are untouched and come next). */
 int lmat_stream_release(lmat_stream* st);
 void lmat_stream_destroy(lmat_stream* st);
+/* Test hook, host bookkeeping only (no kernel, no copy): out6[0] queued submits whose offsets were made on the device
+ * (reads of one length, off[0] == 0), [1] queued submits whose offsets were copied in, [2] submits partitioned on more
+ * than one host thread, [3] submits whose length-class lists were sent (more than one class in use), [4] grow re-runs
+ * so far (a slot whose batch printed more pairs than it holds grows fourfold and runs the batch again), [5] the largest
+ * candidate capacity among the slots, in pairs (at creation cands_per_read x max_reads + 1024 x 2048 each: the second
+ * term is what the sub-cursors may leave unused). */
+int lmat_debug_stream_stats(const lmat_stream* st, uint64_t* out6);
 
 /* ---- tallies (merge step read_label.cpp:1760-1800) --------------------------
  * Dense arrays indexed by the engine's internal taxid index; n_ids = number of

@@ -158,6 +158,8 @@ def load_library(path: str | None = None):
         "lmat_stream_next": (i32, [vp, P(vp), P(vp), P(u64), P(u64), P(u64)]),
         "lmat_stream_release": (i32, [vp]),
         "lmat_stream_destroy": (None, [vp]),
+        "lmat_debug_stream_stats": (i32, [vp, vp]),
+        "lmat_debug_reads_words": (i32, [vp, vp, u64, u64, vp, vp]),
         "lmat_counts_allreduce": (i32, [P(vp), i32]),
         "lmat_comm_unique_id": (i32, [vp]),
         "lmat_comm_init": (i32, [vp, vp, i32, i32]),
@@ -238,7 +240,8 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_cov_summary", "lmat_cov_histogram",
             "lmat_export_create", "lmat_export_destroy", "lmat_export_error", "lmat_export_set_options", "lmat_export_run", "lmat_export_fetch",
             "lmat_export_taxid_counts", "lmat_build_add_db", "lmat_table_unaddress",
-            "lmat_genebuild_create", "lmat_genedb_build_from_genes"]
+            "lmat_genebuild_create", "lmat_genedb_build_from_genes",
+            "lmat_debug_stream_stats", "lmat_debug_reads_words"]
 
 
 def _ptr(a):
@@ -264,6 +267,15 @@ class Reads:
         bases = np.zeros(int(off[-1]) + 1, dtype=np.uint8)
         self.eng._chk(self.eng.lib.lmat_reads_download_ascii(self.eng.ctx, self.h, first, n, _ptr(bases), _ptr(off)))
         return bases[:-1], off
+
+    def words(self, first=0, count=None):
+        """-> (words uint32, rec_off uint64[count+1]): the packed records as they lie on the device, offsets from the first one."""
+        n = len(self) - first if count is None else count
+        ro = np.zeros(n + 1, dtype=np.uint64)
+        self.eng._chk(self.eng.lib.lmat_debug_reads_words(self.eng.ctx, self.h, first, n, None, _ptr(ro)))
+        w = np.zeros(max(int(ro[-1]), 1), dtype=np.uint32)
+        self.eng._chk(self.eng.lib.lmat_debug_reads_words(self.eng.ctx, self.h, first, n, _ptr(w), _ptr(ro)))
+        return w[:int(ro[-1])], ro
 
     def free(self):
         if self.h:
@@ -388,6 +400,19 @@ class Stream:
         self.eng._chk(self.lib.lmat_stream_release(self.h))
         self.in_flight -= 1
         return res, cands, int(tag.value)
+
+    STATS = ("uniform", "general", "threaded", "class_lists", "grow_reruns", "cand_cap")
+
+    def stats(self):
+        """Host bookkeeping (lmat_debug_stream_stats): queued submits by branch, grow re-runs, the largest slot capacity in pairs."""
+        out = np.zeros(6, dtype=np.uint64)
+        self.eng._chk(self.lib.lmat_debug_stream_stats(self.h, _ptr(out)))
+        return dict(zip(self.STATS, (int(x) for x in out)))
+
+    def drop_failed(self):
+        """Releases the oldest batch after next() has raised its error: the batches behind it come next."""
+        self.eng._chk(self.lib.lmat_stream_release(self.h))
+        self.in_flight -= 1
 
     def close(self):
         if self.h:

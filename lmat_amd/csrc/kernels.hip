@@ -468,7 +468,7 @@ __global__ void synth_reads_kernel(uint32_t* words, const uint64_t* __restrict__
                         if ((e % 100) == 0) b = (b + 1 + (uint32_t)((e >> 32) % 3)) & 3u;
                     }
                     bool ok = !(kind == 11 && p == npos);
-                    code |= b << (2 * j);
+                    code |= (ok ? b : 0u) << (2 * j);  // an N carries code 0, as in a record packed from ASCII
                     valid |= (ok ? 1u : 0u) << j;
                 }
                 rec[1 + w] = code;

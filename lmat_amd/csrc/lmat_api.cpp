@@ -1332,6 +1332,16 @@ int lmat_reads_download_ascii(lmat_ctx* c, const lmat_reads* r, uint64_t first, 
     return LMAT_OK;
 }
 
+int lmat_debug_reads_words(lmat_ctx* c, const lmat_reads* r, uint64_t first, uint64_t count, uint32_t* words, uint64_t* rec_off) {
+    if (!c || !r || !rec_off || first + count > r->n) return LMAT_E_ARG;
+    hipSetDevice(c->device);
+    HIPCHK(c, hipMemcpy(rec_off, r->rec_off + first, (count + 1) * 8, hipMemcpyDeviceToHost));
+    const uint64_t w0 = rec_off[0];
+    for (uint64_t i = 0; i <= count; ++i) rec_off[i] -= w0;
+    if (words && rec_off[count]) HIPCHK(c, hipMemcpy(words, r->words + w0, rec_off[count] * 4, hipMemcpyDeviceToHost));
+    return LMAT_OK;
+}
+
 uint64_t lmat_reads_count(const lmat_reads* r) { return r ? r->n : 0; }
 uint64_t lmat_reads_device_bytes(const lmat_reads* r) { return r ? r->n_words * 4 + (r->n + 1) * 8 : 0; }
 void lmat_reads_free(lmat_ctx* c, lmat_reads* r) {
@@ -2108,6 +2118,7 @@ struct lmat_stream {
         hipEvent_t ev_up = nullptr, ev_done = nullptr, ev_out = nullptr;
         uint64_t n = 0, tag = 0;
         int state = 0;               // 0 free, 1 acquired, 2 in flight, 3 handed to the caller
+        bool failed = false;         // in flight, and lmat_stream_next has reported this batch's error
     };
     lmat_ctx* c = nullptr;
     std::vector<Slot> slots;
@@ -2116,6 +2127,8 @@ struct lmat_stream {
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     uint64_t head = 0, tail = 0;     // slot of the next acquire / of the oldest batch in flight (monotonic counters)
     void* d_scratch_counts = nullptr;  // tallies of a re-run go nowhere
+    // host bookkeeping for lmat_debug_stream_stats: queued submits by the branch they took, and grow re-runs
+    uint64_t n_uniform = 0, n_general = 0, n_threaded = 0, n_cls_sent = 0, n_grow = 0;
 };
 
 static void stream_free(lmat_stream* st) {
@@ -2245,6 +2258,7 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         ext_bases += base;
     }
     if (n > st->max_reads || (n && sl.h_off[n] > st->max_bases)) { sl.state = 0; return set_err(c, LMAT_E_ARG, "batch larger than the stream was created for"); }
+    if (sl.cand_cap && (!sl.d_cands || !sl.h_cands)) { sl.state = 0; return set_err(c, LMAT_E_NOMEM, "this slot lost its candidate buffer when it could not grow"); }
     hipSetDevice(c->device);
     // record offsets and the length classes of the fast kernels: two passes over the n offsets, split over a few host
     // threads when the batch is large (2 M reads took 12 ms in one thread, longer than the GPU needs for them)
@@ -2328,6 +2342,9 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         HIPCHK(c, hipEventRecord(sl.ev_up, st->s_h2d));
         HIPCHK(c, hipStreamWaitEvent(c->stream, sl.ev_up, 0));
         lap("copies queued");
+        ++(uniform ? st->n_uniform : st->n_general);
+        st->n_threaded += nt > 1;
+        st->n_cls_sent += used > 1;
         if (uniform) launch_fill_offsets(sl.d_off, sl.reads.rec_off, n, max_len, c->stream);
         launch_pack_reads(sl.d_bases, sl.d_off, sl.reads.rec_off, sl.reads.words, n, c->stream);
         const int rc = stream_launch(st, sl, false);
@@ -2340,6 +2357,7 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         lap("kernels queued");
     }
     sl.state = 2;
+    sl.failed = false;
     ++st->head;
     return LMAT_OK;
 }
@@ -2374,7 +2392,7 @@ int lmat_stream_next(lmat_stream* st, const lmat_read_result** results, const lm
             nc = sl.h_cursor[0];
             if (!(fresh & kErrCandOverflow)) {
                 const DeviceError e = device_error(fresh);
-                if (e.code) return set_err(c, e.code, e.msg);
+                if (e.code) { sl.failed = true; return set_err(c, e.code, e.msg); }
                 break;
             }
             // the batch printed more candidates than the slot holds: grow this slot fourfold and run it again (its packed reads
@@ -2384,9 +2402,20 @@ int lmat_stream_next(lmat_stream* st, const lmat_read_result** results, const lm
             hipFree(sl.d_cands); hipHostFree(sl.h_cands);
             sl.d_cands = nullptr; sl.h_cands = nullptr;
             sl.cand_cap *= 4;
+            ++st->n_grow;
             if (hipMalloc((void**)&sl.d_cands, sl.cand_cap * sizeof(lmat_cand)) != hipSuccess ||
-                hipHostMalloc((void**)&sl.h_cands, sl.cand_cap * sizeof(lmat_cand), hipHostMallocDefault) != hipSuccess)
+                hipHostMalloc((void**)&sl.h_cands, sl.cand_cap * sizeof(lmat_cand), hipHostMallocDefault) != hipSuccess) {
+                // the batch can be dropped like any failed one; the slot goes back to the size it had (a slot left without
+                // its buffers is refused at its next submit)
+                if (sl.d_cands) hipFree(sl.d_cands);
+                if (sl.h_cands) hipHostFree(sl.h_cands);
+                sl.d_cands = nullptr; sl.h_cands = nullptr;
+                sl.cand_cap /= 4;
+                if (hipMalloc((void**)&sl.d_cands, sl.cand_cap * sizeof(lmat_cand)) != hipSuccess) sl.d_cands = nullptr;
+                if (hipHostMalloc((void**)&sl.h_cands, sl.cand_cap * sizeof(lmat_cand), hipHostMallocDefault) != hipSuccess) sl.h_cands = nullptr;
+                sl.failed = true;
                 return set_err(c, LMAT_E_NOMEM, "out of memory growing a candidate buffer");
+            }
             const int rc = stream_launch(st, sl, true);
             if (rc) return rc;
         }
@@ -2411,9 +2440,23 @@ int lmat_stream_next(lmat_stream* st, const lmat_read_result** results, const lm
 int lmat_stream_release(lmat_stream* st) {
     if (!st) return LMAT_E_ARG;
     lmat_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
-    if (sl.state != 3) return set_err(st->c, LMAT_E_ARG, "no batch is checked out");
+    // (a batch whose error lmat_stream_next has reported is dropped the same way: the batches behind it are still good.  Its
+    // result copy may still be queued on the copy-out stream -- ev_out is not waited for --: the next batch through this slot
+    // queues its own copy behind it on that stream, into the same pinned buffer, so the stale records are overwritten before
+    // the caller sees them.)
+    if (sl.state != 3 && !(sl.state == 2 && sl.failed)) return set_err(st->c, LMAT_E_ARG, "no batch is checked out");
     sl.state = 0;
+    sl.failed = false;
     ++st->tail;
+    return LMAT_OK;
+}
+
+int lmat_debug_stream_stats(const lmat_stream* st, uint64_t* out6) {
+    if (!st || !out6) return LMAT_E_ARG;
+    uint64_t cap = 0;
+    for (const auto& sl : st->slots) cap = std::max(cap, sl.cand_cap);
+    const uint64_t v[6] = {st->n_uniform, st->n_general, st->n_threaded, st->n_cls_sent, st->n_grow, cap};
+    for (int i = 0; i < 6; ++i) out6[i] = v[i];
     return LMAT_OK;
 }
 

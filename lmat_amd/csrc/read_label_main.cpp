@@ -885,12 +885,16 @@ int main(int argc, char* argv[]) {
     // and their read counts must be the ones the writer summed on the host in input order
     if (lmat_counts_allreduce(ctxs.data(), n_gpu) != LMAT_OK) { std::cerr << "ERROR! merge: " << lmat_last_error(ctx) << std::endl; destroy_all(); return -1; }
     {
-        std::vector<uint32_t> tids(70000);
-        std::vector<uint64_t> cnts(70000);
+        // sized from the context: a wide taxonomy calls more distinct taxids than any fixed number (lmat_counts_get reports the
+        // number of tallied ids uncapped and fills at most `cap` of them)
+        uint32_t cap = 0;
+        bool same = lmat_counts_layout(ctx, &cap, nullptr) == LMAT_OK;
+        std::vector<uint32_t> tids(std::max<uint32_t>(cap, 1));
+        std::vector<uint64_t> cnts(std::max<uint32_t>(cap, 1));
         uint32_t nz = 0;
         uint64_t nm3[3] = {0, 0, 0};
-        bool same = lmat_counts_get(ctx, tids.data(), cnts.data(), nullptr, 70000, &nz, nm3) == LMAT_OK && nz == merge_count.size();
-        for (uint32_t i = 0; same && i < nz; ++i) same = merge_count.count(tids[i]) && (uint64_t)merge_count[tids[i]] == cnts[i];
+        same = same && lmat_counts_get(ctx, tids.data(), cnts.data(), nullptr, cap, &nz, nm3) == LMAT_OK && nz <= cap && nz == merge_count.size();
+        for (uint32_t i = 0; same && i < std::min(nz, cap); ++i) same = merge_count.count(tids[i]) && (uint64_t)merge_count[tids[i]] == cnts[i];
         for (int j = 0; same && j < 3; ++j) same = (uint64_t)(nomatch_merge.count(j) ? nomatch_merge[j] : 0) == nm3[j];
         if (!same) { std::cerr << "ERROR! the merged device tallies differ from the per-record tallies" << std::endl; destroy_all(); return -1; }
     }

@@ -277,3 +277,47 @@ def test_cli_with_a_taxonomy_above_16_bits(small_dataset, tmp_path):
     _run_cli(big_ds, str(tmp_path / "b"), ds["fasta"], 1)
     for suffix in ("0.out", ".0.30.fastsummary", ".0.30.nomatchsum"):
         assert open(str(tmp_path / "a") + suffix).read() == open(str(tmp_path / "b") + suffix).read(), suffix
+
+
+def test_cli_calls_more_than_70000_distinct_taxids(tmp_path):
+    """A star taxonomy -- 70 100 leaves under the root, no -f map -- with one private 20-mer per leaf and one 20-base read per
+    leaf, at -j 1: every read is called on its own leaf, so the run tallies more distinct taxids than the 70 000 the end-of-run
+    tally check once had room for.  The .out is the oracle's; the .fastsummary is known in closed form: one line per leaf, one
+    read each.  Nothing is trimmed: 70 100 reads of one k-mer are the smallest files that get there (a few seconds, most of it
+    writing the files)."""
+    import numpy as np
+    import oracle_py
+    from lmat_amd import synth
+    n = 70100                                       # leaves 100000, 100003 ... 310297: none of the taxids read_label treats specially
+    tax = synth.Taxonomy()
+    tax.add(1, 1, "no_rank", "root")
+    for i in range(n):
+        tax.add(100000 + 3 * i, 1, "species", "s%d" % i)
+    tax.id16 = dict.fromkeys(tax.ids, 1)            # (write_aux_files writes a 32->16 map too; the run has no -f and never reads it)
+    p = synth.write_aux_files(str(tmp_path), tax)
+    # leaf i owns A <i in nine base-4 digits> CCCCCCCCC A: the reverse complement starts with T, so the forward k-mer is the
+    # canonical one and no k-mer is the reverse complement of another
+    digits = (np.arange(n)[:, None] >> (2 * np.arange(8, -1, -1))) & 3
+    codes = np.concatenate([np.zeros((n, 1), int), digits, np.ones((n, 9), int), np.zeros((n, 1), int)], axis=1)
+    kmers = (codes.astype(np.uint64) << (2 * np.arange(19, -1, -1)).astype(np.uint64)).sum(axis=1).astype(np.uint64)
+    assert (np.diff(kmers.astype(np.int64)) > 0).all()
+    db = str(tmp_path / "star.bin")
+    synth.write_taxhisto(db, kmers, [[100000 + 3 * i] for i in range(n)], 20)
+    fa = str(tmp_path / "star.fa")
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+    with open(fa, "w") as f:
+        f.write("".join(">r%d\n%s\n" % (i, s) for i, s in enumerate(letters[codes].view("S20").ravel().astype(str))))
+    out = str(tmp_path / "o")
+    r = subprocess.run([EXE, "-u", p["names"], "-w", p["rank"], "-x", "0", "-j", "1", "-l", "0", "-b", "1.0", "-e", p["depth"], "-p", "-t", "1",
+                        "-i", fa, "-d", db, "-c", p["tree"], "-o", out], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:] + r.stdout[-2000:]
+    rows = [l.split("\t") for l in open(out + ".0.1.fastsummary").read().splitlines()]
+    called = {int(x[2]): int(x[1]) for x in rows}
+    assert len(called) == len(rows) == n > 70000 and set(called) == set(tax.ids[1:]) and set(called.values()) == {1}
+    orc = oracle_py.Oracle(p["tree"], p["depth"], p["rank"], None)
+    orc.add_taxhisto(db)
+    orc.set_options(min_kmer=1)
+    want, _, _ = orc.run_file(fa, 20, p["names"])
+    orc.close()
+    got = open(out + "0.out").read()
+    assert got.count("\n") == n and got == want

@@ -926,8 +926,9 @@ def test_failed_blocking_launch_leaves_the_tallies_alone(small_dataset):
 # ---- streamed boundary (lmat_stream_*) and the cross-context merge ------------------------------------------
 @pytest.mark.parametrize("prn_all", [1, 0])
 def test_stream_equals_blocking_path(config1, prn_all):
-    """Batches pushed through the ring of pinned slots (mixed lengths, several batches in flight, a candidate buffer
-    that is too small at first) give the text and tallies of the blocking path."""
+    """Batches pushed through the ring of pinned slots (mixed lengths, several batches in flight) give the text and tallies of
+    the blocking path.  A slot holds cands_per_read * max_reads + 1024 * 2048 pairs, far more than a thousand of these reads
+    print: no slot grows here (asserted) -- the grow path has tests of its own in test_gpu_stream_edges.py."""
     from lmat_amd import Engine, Params, Stream
     eng = _engine(config1, Params.run_rl(prn_all=prn_all))
     reads = config1["reads"][:6000]
@@ -939,7 +940,7 @@ def test_stream_equals_blocking_path(config1, prn_all):
     tallies0 = eng.counts()
     dr.free()
     eng.counts_reset()
-    st = Stream(eng, max_reads=1000, max_bases=1000 * 300, cands_per_read=2, n_slots=3)   # 2 per read: forces the grow path
+    st = Stream(eng, max_reads=1000, max_bases=1000 * 300, cands_per_read=2, n_slots=3)
     bounds = list(range(0, len(reads), 1000)) + [len(reads)]
     got, pending = {}, 0
     for bi, (lo, hi) in enumerate(zip(bounds, bounds[1:])):
@@ -960,6 +961,7 @@ def test_stream_equals_blocking_path(config1, prn_all):
         text += eng.format_out(r, cd, (np.append(blob[int(off[lo]):int(off[hi])], np.uint8(0)), o), first_index=lo)
     assert text == want
     assert eng.counts() == tallies0
+    assert st.stats()["grow_reruns"] == 0 and st.stats()["cand_cap"] == 2 * 1000 + 1024 * 2048
     st.close()
     eng.close()
 
