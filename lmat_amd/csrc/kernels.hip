@@ -1931,13 +1931,20 @@ __global__ __launch_bounds__(256) void tail_kernel(ClassifyArgs A) {
     ((u32x4*)A.tail16)[ri * LPR + j] = e;
 }
 
+// words of the record of a read of k + 128 .. k + 131 bases at k = 20 (148 .. 151): the length, 10 code words, 5 validity words
+static const uint32_t kUniRecWords = 16;
 typedef const ClassifyArgs __attribute__((address_space(4))) CArgs;
 // PLAIN (the 160-k-mer fast class only; launch_classify_t picks it per launch, plain_launch() is the list): the launch is the plain
 // run -- k = 20 in the compact layout (m = 17, two low bits), no null model, no -p candidates, no human bias, no rand / gene mode, no
 // debug stop, the decision on the wave and not by rows, every read of the batch taken in batch order, tails of four entries.  What
 // such a launch fixes is a literal here instead of a load through Ap, a compare and a branch per read, and the arms it cannot take
 // are not compiled.  No statement changes: PLAIN == false is the code as it was.
-template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false>
+// UNI (a PLAIN launch whose reads all have k + 128 .. k + 131 bases, their records laid end to end from word 0 -- an untrimmed
+// run of 150 bp reads; uniform_launch() below): the record geometry is a literal too.  Every read has two full chunks and a tail
+// of one to four positions that tail_kernel looked up, 10 code words and 5 validity words; the chunk loops lose their `break`s,
+// the third chunk's own lookup is not compiled, and the read loop computes record offsets instead of loading them.  The length
+// itself, the tail's lane mask and every threshold stay run-time values.  UNI == false is the code as it was.
+template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false, bool UNI = false>
 __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned char* lds, LAS unsigned char* xl, int lane,
                                              const uint32_t* wcur, uint32_t (&nmacc)[2]) {
     using L = WL<U, T, E, INK4, CPT, WIDE>;
@@ -2007,6 +2014,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     uint8_t* el_fl = (uint8_t*)(el_plen + E);    // flags[ta]
 
     static_assert(!PLAIN || (U == 160 && CPT && !INK4 && !PERM && !WIDE && !LMAT_ABLATE), "PLAIN is a variant of the headline class");
+    static_assert(!UNI || PLAIN, "UNI is a variant of PLAIN");
     const int k = PLAIN ? 20 : tb.k;
     const GAS uint64_t* g_slots = (const GAS uint64_t*)tb.slots;
     const GAS uint16_t* g_arena = (const GAS uint16_t*)tb.arena;
@@ -2046,13 +2054,13 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         out[4] = (uint64_t)z | ((uint64_t)(uint32_t)bin_sel << 32);          // n_cand, bin_sel
     };
 
-    if ((int)len < k) {  // proc_line :1217-1223
+    if (!UNI && (int)len < k) {  // proc_line :1217-1223
         if (lane == 0) { emit(LMAT_ST_SHORT_LEN, 0); nmacc[0]++; }
         return;
     }
     const uint32_t P = len - k + 1;
     if (!PLAIN && (P < A.p_min || P > A.p_max)) return;  // another launch over the same list takes this read
-    if (P > (uint32_t)U) {  // the host sizes U from the batch's longest read
+    if (!UNI && P > (uint32_t)U) {  // the host sizes U from the batch's longest read
         if (lane == 0) {
             emit(255, 0);
             if (A.ovf_list) ((GAS uint32_t*)A.ovf_list)[G_ADD(&g_cursor[A.ovf_slot], 1u)] = (uint32_t)r;  // re-run by a larger class
@@ -2064,13 +2072,13 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     // 32-bit scalar (re-deriving it at each of the three places that ask was two scalar loads and a dozen scalar instructions a time).
     constexpr bool TAILOK = CPT && U == 160 && !INK4;
     uint32_t tail_flag = 0;
-    if constexpr (TAILOK) {
+    if constexpr (TAILOK && !UNI) {
         const uint32_t lpr = PLAIN ? 4u : A.tail_lpr;
         tail_flag = (uint32_t)__builtin_amdgcn_readfirstlane((lpr != 0 && P > 128u && P <= 128u + lpr && !(PLAIN ? 0u : A.nm.active)) ? 1 : 0);  // (a scalar, not a lane mask re-materialised from its conditions)
     }
-    auto tail_mode = [&]() -> bool { return TAILOK && tail_flag != 0; };
+    auto tail_mode = [&]() -> bool { return TAILOK && (UNI || tail_flag != 0); };
     // ---- packed record -> LDS (coalesced), zero tail so windows past the end are invalid
-    const uint32_t nb = (len + 15) / 16, nm = (len + 31) / 32;
+    const uint32_t nb = UNI ? 10u : (len + 15) / 16, nm = UNI ? 5u : (len + 31) / 32;
 #pragma unroll
     for (int j = 0; j < (L::RD_WORDS + 1 + 63) / 64; ++j) {
         const uint32_t w = (uint32_t)lane + 64u * j;  // record word index; rd[] starts at word 1
@@ -2243,7 +2251,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     if (CACHE) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-            if ((uint32_t)c * 64 >= len) break;
+            if (!UNI && (uint32_t)c * 64 >= len) break;
             if (TAILOK && c == 2 && tail_mode()) {  // looked up beforehand: k-mer, bucket, minimizer offset; the payload goes straight to its place
                 const uint32_t lpr = PLAIN ? 4u : A.tail_lpr;
                 const uint64_t ri = r - A.result_base;
@@ -2274,7 +2282,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             }
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
-                if ((uint32_t)c * 64 >= P) break;
+                if (!UNI && (uint32_t)c * 64 >= P) break;
                 if (TAILOK && c == 2 && tail_mode()) continue;
                 cpt_finish(c, kreg[c], ureg[c], c + 1 < CH ? ureg[c + 1] : 0ull, fcm[c], hreg[c], treg[c]);
             }
@@ -2313,7 +2321,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     if (CACHE) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-            if ((uint32_t)c * 64 >= P) break;
+            if (!UNI && (uint32_t)c * 64 >= P) break;
             pass2_chunk((uint32_t)c * 64, kreg[c], hreg[c], lane_bit(okm[c]));
         }
     } else {
@@ -2447,7 +2455,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             if (lane < 3) { barr[lane] = 0u; sarr[lane] = kNone; qarr[lane] = 0xFFFF; }
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
-                if ((uint32_t)c * 64 >= P) break;
+                if (!UNI && (uint32_t)c * 64 >= P) break;
                 barr[3 + c * 64 + lane] = hreg[c];
                 sarr[3 + c * 64 + lane] = lane_bit(okm[c]) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
                 qarr[3 + c * 64 + lane] = lane_bit(okm[c]) ? (uint16_t)((uint32_t)c * 64 + lane + (treg[c] >> 30)) : (uint16_t)0xFFFF;
@@ -2456,7 +2464,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-            if ((uint32_t)c * 64 >= P) break;
+            if (!UNI && (uint32_t)c * 64 >= P) break;
             const uint64_t V = okm[c];
             const uint32_t b = hreg[c];
             const uint32_t sig = lane_bit(V) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
@@ -2502,7 +2510,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         if (CACHE) {
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
-                if ((uint32_t)c * 64 >= P) break;
+                if (!UNI && (uint32_t)c * 64 >= P) break;
                 const bool ok = lane_bit(okm[c]);
                 uint32_t h = 0;
                 if (ok) h = lds_min_insert(hv, L::H - 1, kreg[c], (uint32_t)c * 64 + lane);
@@ -2511,7 +2519,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             WSYNC();
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
-                if ((uint32_t)c * 64 >= P) break;
+                if (!UNI && (uint32_t)c * 64 >= P) break;
                 const bool ok = lane_bit(okm[c]);
                 firstm[c] = __ballot(ok && (uint32_t)(hv[(treg[c] >> 16) & 0x3FFFu] & 0xFFFF) == (uint32_t)c * 64 + lane);
                 nuniq += popc64(firstm[c]);
@@ -2528,7 +2536,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     } else {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-            if ((uint32_t)c * 64 >= P) break;
+            if (!UNI && (uint32_t)c * 64 >= P) break;
             firstm[c] = okm[c];
             nuniq += popc64(okm[c]);
         }
@@ -2636,7 +2644,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             if (g0 + 32 < ng) WSYNC();  // the next round overwrites the stage
         }
         static_assert(kCptOvfFlag == 0x80000000u, "the spill flag is the sign bit");
-        if (p < P) upay[p] = lane_bit(firstmask) ? pay : 0u;
+        if (UNI || p < P) upay[p] = lane_bit(firstmask) ? pay : 0u;  // (UNI: chunks 0 and 1 only, always full)
         const uint64_t pm = firstmask & __ballot((int32_t)spillw < 0);
         if (pm) {
             if (nov + (uint32_t)popc64(pm) > 64u) { WSYNC(); ovf_pass(); WSYNC(); }  // the list holds 64 entries: one chunk's worth
@@ -2648,7 +2656,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     if (CACHE) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-            if ((uint32_t)c * 64 >= P) break;
+            if (!UNI && (uint32_t)c * 64 >= P) break;
             if (TAILOK && c == 2 && tail_mode()) {  // the payloads are in place; a repeat of an earlier k-mer of the read gives its own up
                 if (suspect && 128u + (uint32_t)lane < P && !lane_bit(firstm[c])) upay[128 + lane] = 0u;
                 WSYNC();
@@ -3989,7 +3997,7 @@ __global__ __launch_bounds__(64) void gather_bench_kernel(const uint64_t* __rest
 #define LMAT_FAST_WAVES 8   // (A/B builds: -DLMAT_FAST_WAVES=7 compiles the fast classes for 7 waves per SIMD, 72 registers)
 #endif
 constexpr int classify_waves(int U, int E, bool INK4, bool CPT) { return INK4 ? 1 : (E > kFastE ? (U <= 160 ? 5 : 2) : (U <= 160 ? (CPT ? LMAT_FAST_WAVES : 5) : (U <= 256 ? (CPT ? LMAT_FAST_WAVES : 5) : (U <= 320 ? (CPT ? 5 : 3) : (CPT ? 4 : 3))))); }
-template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false>
+template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false, bool UNI = false>
 __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_kernel(ClassifyArgs A) {
     extern __shared__ __align__(16) unsigned char lds_smem[];
     // U > 2048: the per-read tables of this workgroup live in global memory
@@ -4008,6 +4016,24 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
     uint32_t wcur[NW], wnext[NW];
     uint32_t nmacc[2] = {0, 0};
     uint64_t off1 = 0;
+    if constexpr (UNI) {
+        // UNI: record r is the 16 words from 16 * r -- no offsets to fetch, the next read's words are asked for one read ahead
+        static_assert(!UNI || NW == 1, "a UNI record is one wave-load");
+        if (it >= A.count) return;
+        wcur[0] = ((const GAS uint32_t*)A.words)[kUniRecWords * (A.first + it) + lane];  // (runs past the record: the buffer is padded)
+        while (true) {
+            CArgs* Ap = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(Ap));  // (a fresh look at the arguments every trip, as below)
+            const uint64_t r = Ap->first + it;
+            const bool more = (uint64_t)it + G < Ap->count;
+            wnext[0] = more ? ((const GAS uint32_t*)Ap->words)[kUniRecWords * (r + G) + lane] : 0u;
+            classify_one<U, T, E, INK4, PERM, CPT, WIDE, PLAIN, UNI>(Ap, r, smem, xl, lane, wcur, nmacc);
+            WSYNC();
+            wcur[0] = wnext[0];
+            if (!more) break;
+            it += G;
+        }
+    } else {
     {
         const uint64_t count = !PLAIN && A.count_ptr ? (uint64_t)*(const GAS uint32_t*)A.count_ptr : A.count;
         if (it >= count) return;
@@ -4039,6 +4065,7 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
         off1 = off2;
         if (!more) break;
         it += G;  // (below count <= 2^32 - 1: no wrap)
+    }
     }
     if (lane == 0) {  // ReadTooShort / NoDbHits counts of this wave's reads, one atomic each
         GAS unsigned long long* tally_nomatch = (GAS unsigned long long*)A.counts + 2 * (uint64_t)A.tb.n_ids;
@@ -4227,16 +4254,24 @@ static bool plain_launch(const ClassifyArgs& a, int k4_static) {
            !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 5 && !a.cands && a.prm.hbias == 0.0f &&
            a.p_min == 0 && a.p_max == 0xFFFFFFFFu && !a.index && !a.count_ptr && a.tail_lpr == 4;
 }
+// The plain run over records of one geometry (classify_one's UNI): a.uniform is the host's word that every read of the launch has
+// k + 128 .. k + 131 bases and that record r starts at word kUniRecWords * r (lmat_api.cpp uniform_reads; no device memory is
+// read for it).  LMAT_UNIFORM=0 sends such launches to PLAIN.
+static bool uniform_launch(const ClassifyArgs& a) {
+    static const bool on = !getenv("LMAT_UNIFORM") || atoi(getenv("LMAT_UNIFORM")) != 0;
+    return on && a.uniform;
+}
 // launches of <160, 64, kFastE> on a compact 16-bit table without -s (the class PLAIN is a variant of) by kernel, per device: [0] the
-// generic instantiation, [1] PLAIN (lmat_debug_variant_launches)
-static std::atomic<unsigned long long> g_variant_launches[64][2];
+// generic instantiation, [1] PLAIN, UNI included (lmat_debug_variant_launches), [2] UNI alone (lmat_debug_uniform_launches)
+static std::atomic<unsigned long long> g_variant_launches[64][3];
 void classify_variant_launches(int device, uint64_t out[2]) {
     out[0] = out[1] = 0;
     if (device < 0 || device >= 64) return;
     out[0] = g_variant_launches[device][0].load();
     out[1] = g_variant_launches[device][1].load();
 }
-template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false>
+uint64_t classify_uniform_launches(int device) { return device < 0 || device >= 64 ? 0 : g_variant_launches[device][2].load(); }
+template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false, bool UNI = false>
 static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     using L = WL<U, T, E, INK4, CPT, WIDE>;
     ClassifyArgs a = a_in;
@@ -4244,11 +4279,18 @@ static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     // the instantiation the variant belongs to: only its launches are asked about, and only they are counted
     constexpr bool kPlainClass = U == 160 && T == 64 && E == kFastE && !INK4 && !PERM && CPT && !WIDE;
     if constexpr (kPlainClass && !PLAIN && !LMAT_ABLATE) {
-        if (plain_launch(a, a.prm.k4_static)) { launch_classify_t<U, T, E, INK4, PERM, CPT, WIDE, true>(a_in, stream); return; }
+        if (plain_launch(a, a.prm.k4_static)) {
+            if (uniform_launch(a)) launch_classify_t<U, T, E, INK4, PERM, CPT, WIDE, true, true>(a_in, stream);
+            else launch_classify_t<U, T, E, INK4, PERM, CPT, WIDE, true>(a_in, stream);
+            return;
+        }
     }
     if constexpr (kPlainClass) {
         int dev = 0;   // (the current device, asked for as PerDeviceOnce does)
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) g_variant_launches[dev][PLAIN ? 1 : 0]++;
+        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+            g_variant_launches[dev][PLAIN ? 1 : 0]++;
+            if (UNI) g_variant_launches[dev][2]++;
+        }
     }
     if (U > 2048) {  // tables in global memory: few workgroups; LDS only for the compact probe's scratch block
         int grid = kGmemGrid;
@@ -4259,7 +4301,7 @@ static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     static const int lds_pad = getenv("LMAT_LDS_PAD") ? atoi(getenv("LMAT_LDS_PAD")) : 0;  // experiments: fewer resident waves
     const int lds_bytes = L::BYTES + lds_pad;
     static PerDeviceOnce attr_once;
-    attr_once([lds_bytes] { hipFuncSetAttribute((const void*)classify_kernel<U, T, E, INK4, PERM, CPT, WIDE, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
+    attr_once([lds_bytes] { hipFuncSetAttribute((const void*)classify_kernel<U, T, E, INK4, PERM, CPT, WIDE, PLAIN, UNI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); });
     // one single-wave workgroup per read slot; enough groups to fill every CU's LDS several times over
     const int per_cu = 160 * 1024 / lds_bytes;
     // Reads differ in cost (one over genus-shared k-mers takes 3-4 times the usual), and a block keeps its share of the batch:
@@ -4270,7 +4312,7 @@ static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     if (!a.count_ptr && (uint64_t)grid > a.count) grid = (int)a.count;
     if (a.count_ptr && INK4 && grid > 256 * (per_cu < 2 ? 2 : per_cu)) grid = 256 * (per_cu < 2 ? 2 : per_cu);  // the lists of the large classes are short (the E = 512 class may get a tenth of a batch): a block per wave the LDS holds
     if (grid < 1) grid = 1;
-    classify_kernel<U, T, E, INK4, PERM, CPT, WIDE, PLAIN><<<dim3(grid), dim3(64), lds_bytes, stream>>>(a);
+    classify_kernel<U, T, E, INK4, PERM, CPT, WIDE, PLAIN, UNI><<<dim3(grid), dim3(64), lds_bytes, stream>>>(a);
 }
 
 void launch_k4_debug(const ClassifyArgs& a, const uint32_t* idx, const float* scores, const uint64_t* off, const float* stdevs, uint64_t n,

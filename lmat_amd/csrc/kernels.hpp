@@ -47,6 +47,9 @@ struct ClassifyArgs {
     const uint32_t* tail16 = nullptr;  // [reads][tail_lpr] x 16 B: k-mer lo | k-mer hi | bucket | payload, valid << 24, minimizer offset << 30
     const uint64_t* tail_u = nullptr;  // [reads][4]: the scrambled m-mers at positions 128..130 (what the k-mers at 125..127 need)
     uint32_t tail_lpr = 0;
+    // The host knows (from the lengths it laid the records out by, never from device memory) that every read of the launch has
+    // k + 128 .. k + 131 bases and that the record of read r is the 16 words from 16 * r: the geometry the UNI variant folds.
+    uint32_t uniform = 0;
 };
 
 // record handed to the K4 kernels: word0 = nT | cand << 16, word1 reserved, then K4T words reg | cnt << 16
@@ -112,6 +115,8 @@ void launch_k4_debug_counts(const ClassifyArgs& a, const uint32_t* idx, const ui
                             bool on_the_wave, hipStream_t stream, const uint32_t* shape = nullptr, uint8_t* took = nullptr);
 // launches of the 160-k-mer fast class (compact table, 16-bit ids, no -s) on `device` so far, by kernel: out[0] the generic instantiation, out[1] the PLAIN variant
 void classify_variant_launches(int device, uint64_t out[2]);
+// ... of those counted under PLAIN, the launches of its UNI variant (records of one geometry)
+uint64_t classify_uniform_launches(int device);
 int classify_max_read_len();
 size_t classify_gmem_scratch_bytes();
 // issues ~n_probes random bucket reads (rounded up to 144 per wave x 4096 waves)

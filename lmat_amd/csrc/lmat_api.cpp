@@ -1235,11 +1235,12 @@ int lmat_synth_read_windows(lmat_ctx* c, const uint32_t* lengths, uint32_t n_len
 }
 
 // ---------------------------------------------------------------------------------- reads
-static int reads_alloc(lmat_ctx* c, const std::vector<uint64_t>& rec_off, uint32_t max_len, lmat_reads** out) {
+static int reads_alloc(lmat_ctx* c, const std::vector<uint64_t>& rec_off, uint32_t max_len, uint32_t min_len, lmat_reads** out) {
     lmat_reads* r = new lmat_reads();
     r->n = rec_off.size() - 1;
     r->n_words = rec_off.back();
     r->max_len = max_len;
+    r->min_len = r->n ? min_len : 0;
     if (hipMalloc((void**)&r->words, std::max<uint64_t>(r->n_words, 1) * 4 + 16384) != hipSuccess ||  // kernels read whole-record tiles: pad
         hipMalloc((void**)&r->rec_off, rec_off.size() * 8) != hipSuccess) {
         if (r->words) hipFree(r->words);
@@ -1255,16 +1256,17 @@ int lmat_reads_upload(lmat_ctx* c, const uint8_t* bases, const uint64_t* off, ui
     if (!c || !out || (n && (!bases || !off))) return LMAT_E_ARG;
     hipSetDevice(c->device);
     std::vector<uint64_t> rec_off(n + 1, 0);
-    uint32_t max_len = 0;
+    uint32_t max_len = 0, min_len = 0xFFFFFFFFu;
     std::vector<uint32_t> lens(n);
     for (uint64_t i = 0; i < n; ++i) {
         const uint64_t len = off[i + 1] - off[i];
         if (len > 0x7FFFFFFF) return set_err(c, LMAT_E_ARG, "read too long");
         max_len = std::max<uint32_t>(max_len, (uint32_t)len);
+        min_len = std::min<uint32_t>(min_len, (uint32_t)len);
         lens[i] = (uint32_t)len;
         rec_off[i + 1] = rec_off[i] + rec_words((uint32_t)len);
     }
-    int rc = reads_alloc(c, rec_off, max_len, out);
+    int rc = reads_alloc(c, rec_off, max_len, min_len, out);
     if (rc) return rc;
     (*out)->lens = lens;
     if (!n) return LMAT_OK;
@@ -1287,15 +1289,16 @@ int lmat_reads_synth(lmat_ctx* c, uint64_t n, const uint32_t* lengths, uint32_t 
     // the kernel picks lengths[(h>>48) % n_lengths]; offsets must match, so mirror that choice here
     std::vector<uint64_t> rec_off(n + 1, 0);
     std::vector<uint32_t> lens(n);
-    uint32_t max_len = 0;
+    uint32_t max_len = 0, min_len = 0xFFFFFFFFu;
     for (uint64_t r = 0; r < n; ++r) {
         const uint64_t h0 = splitmix(seed ^ (r * 0x9E3779B97F4A7C15ull));
         const uint32_t len = lengths[(uint32_t)((h0 >> 48) % n_lengths)];
         lens[r] = len;
         max_len = std::max(max_len, len);
+        min_len = std::min(min_len, len);
         rec_off[r + 1] = rec_off[r] + rec_words(len);
     }
-    int rc = reads_alloc(c, rec_off, max_len, out);
+    int rc = reads_alloc(c, rec_off, max_len, min_len, out);
     if (rc) return rc;
     (*out)->lens.swap(lens);
     uint32_t* d_len = nullptr;
@@ -1373,6 +1376,15 @@ static int ensure_scratch(lmat_ctx* c, BatchSet& s, uint64_t count) {
     return LMAT_OK;
 }
 
+// Every read of the set has k + 128 .. k + 131 bases (two full 64-lane chunks of k-mer positions and a tail of one to four) and a
+// record of 16 words -- 148 .. 151 bases at k = 20 --, so with the records laid end to end from word 0, as every maker of a read
+// set lays them, record r starts at word 16 * r: what the UNI variant of the headline kernel folds (kernels.hip).  From the
+// lengths the host laid the records out by; min_len == 0 (a set made without it) says no.
+static bool uniform_reads(const lmat_ctx* c, const lmat_reads* r) {
+    const uint32_t k = (uint32_t)c->dev.k;
+    return r->n && r->min_len >= k + 128 && r->max_len <= k + 131 && rec_words(r->min_len) == 16 && rec_words(r->max_len) == 16;
+}
+
 static ClassifyArgs make_args(lmat_ctx* c, const BatchSet& s, const lmat_reads* reads, uint64_t first, uint64_t count, bool want_cands,
                               uint64_t cand_cap) {
     ClassifyArgs a;
@@ -1415,6 +1427,7 @@ static ClassifyArgs make_args(lmat_ctx* c, const BatchSet& s, const lmat_reads* 
     a.ovf_list = s.ovf[0].as<uint32_t>();
     a.ovf_slot = kCurOvfFast;
     a.count_ptr = nullptr;
+    a.uniform = uniform_reads(c, reads) ? 1u : 0u;
     a.k4buf = s.k4buf.as<uint32_t>();
     a.gscratch = nullptr;
     a.rand_max = nullptr;
@@ -2020,6 +2033,13 @@ int lmat_debug_variant_launches(lmat_ctx* c, uint64_t* out2) {
     classify_variant_launches(c->device, out2);
     return LMAT_OK;
 }
+// ... and how many of the launches counted in out2[1] ran as its fixed-geometry variant (kernels.hip uniform_launch; LMAT_UNIFORM=0
+// turns it off)
+int lmat_debug_uniform_launches(lmat_ctx* c, uint64_t* out) {
+    if (!c || !out) return LMAT_E_ARG;
+    *out = classify_uniform_launches(c->device);
+    return LMAT_OK;
+}
 
 int lmat_last_timing(const lmat_ctx* c, float* classify_ms, float* decide_ms, uint64_t* launches) {
     if (!c) return LMAT_E_ARG;
@@ -2324,6 +2344,7 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
     sl.reads.n = n;
     sl.reads.n_words = sl.h_rec_off[n];
     sl.reads.max_len = max_len;
+    sl.reads.min_len = n ? min_len : 0;   // (the slot's records start at word 0 whatever its offsets start at: pass2 and launch_fill_offsets)
     const int used = (cn[0] != 0) + (cn[1] != 0) + (cn[2] != 0) + (cn[3] != 0);
     for (int j = 0; j < kNCls; ++j) sl.reads.cls_n[j] = used > 1 ? cn[j] : 0;
     if ((int)max_len > classify_max_read_len()) {  // refused before anything is queued: the slot goes back untouched

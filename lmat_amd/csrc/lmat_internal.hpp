@@ -124,6 +124,7 @@ struct lmat_reads {
     uint64_t n = 0;
     uint64_t n_words = 0;
     uint32_t max_len = 0;
+    uint32_t min_len = 0;         // shortest read (0: not known, or no reads)
     // Length classes of the fast kernel (k-mer capacities 160 / 256 / 320 / 512: lmat::kNCls, lmat::len_class): read indices per class, ascending, so a
     // mixed-length batch runs each read in the smallest class that holds it.  Built on first use for the database's k.
     std::vector<uint32_t> lens;
