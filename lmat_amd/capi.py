@@ -170,6 +170,7 @@ def load_library(path: str | None = None):
         "lmat_debug_decide": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "lmat_debug_decide_counts": (i32, [vp, vp, vp, vp, vp, u64, i32, vp]),
         "lmat_debug_decide_chain": (i32, [vp, vp, vp, vp, vp, vp, vp, u64, i32, vp, vp]),
+        "lmat_debug_decide_shape": (i32, [vp, vp, vp, vp, vp, vp, u64, i32, vp, vp]),
         "lmat_synth_window": (i32, [vp, u32, u64, P(u64), vp, u32, P(u32)]),
         "lmat_debug_last_counters": (i32, [vp, vp]),
         "lmat_debug_probe_stats": (i32, [vp, vp, u64, vp]),
@@ -233,7 +234,7 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_counts_reset", "lmat_counts_layout", "lmat_counts_device_ptr", "lmat_counts_get", "lmat_gather_bench",
             "lmat_table_address", "lmat_format_out", "lmat_stream_create", "lmat_stream_acquire", "lmat_stream_submit", "lmat_stream_submit_from", "lmat_host_alloc", "lmat_host_free",
             "lmat_stream_next", "lmat_stream_release", "lmat_stream_destroy", "lmat_counts_allreduce",
-            "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_debug_decide_chain", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check", "lmat_debug_variant_launches", "lmat_debug_uniform_launches",
+            "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_debug_decide_chain", "lmat_debug_decide_shape", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check", "lmat_debug_variant_launches", "lmat_debug_uniform_launches",
             "lmat_build_create", "lmat_build_destroy", "lmat_build_error", "lmat_build_set_options", "lmat_build_add_fasta", "lmat_build_add_sequence",
             "lmat_build_run", "lmat_build_write_taxhisto", "lmat_build_fetch", "lmat_db_build_from_genomes",
             "lmat_build_add_taxhisto", "lmat_build_merge_stats", "lmat_build_taxid_counts",
@@ -1060,6 +1061,22 @@ class Engine:
         took = np.zeros(cand.size, dtype=np.uint8)
         self._chk(self.lib.lmat_debug_decide_chain(self.ctx, _ptr(tids), _ptr(counts), _ptr(off), _ptr(cand), _ptr(kept), _ptr(eligible),
                                                    cand.size, int(with_cands), _ptr(res), _ptr(took)))
+        return res, took
+
+    def debug_decide_shape(self, tids, counts, off, cand, shape, with_cands=False):
+        """debug_decide_counts on the wave with the closure's word per table as the classify kernel forms it: shape[i] = kept << 8 |
+        1 << 17 (the closure finished), | eligible | 1 << 16 (it found one eligible id and registered its chain), or 0 -> (results,
+        took): took[i] = 0 where the general code decided table i, 1 the closed form for one lineage, 2 the one for a dominant lineage."""
+        tids = np.ascontiguousarray(tids, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        cand = np.ascontiguousarray(cand, dtype=np.uint32)
+        shape = np.ascontiguousarray(shape, dtype=np.uint32)
+        assert shape.size == cand.size and off.size == cand.size + 1
+        res = np.zeros(cand.size, dtype=READ_RESULT_DTYPE)
+        took = np.zeros(cand.size, dtype=np.uint8)
+        self._chk(self.lib.lmat_debug_decide_shape(self.ctx, _ptr(tids), _ptr(counts), _ptr(off), _ptr(cand), _ptr(shape), cand.size,
+                                                   int(with_cands), _ptr(res), _ptr(took)))
         return res, took
 
     def clone_db_from(self, src: "Engine"):

@@ -1133,6 +1133,45 @@ __device__ __forceinline__ void k4_wave_record(CArgsK4* Ap, int lane, GAS uint64
         }
     }
 }
+// The statistics of a table decided in closed form (:803-880): the general path's own, operand for operand -- the same quotients,
+// the sums in registration order, sqrtf --, without the rank count that rides in its loop.  -> this lane's score; log_avg, stdev1.
+__device__ __forceinline__ float k4_wave_stats(int lane, uint32_t nT, uint32_t cand, uint32_t my_cnt, uint32_t* xch, float& log_avg, float& stdev1) {
+    float* xs = (float*)xch;          // [64] scores by slot, [64] squared deviations: as k4_wave lays them out
+    float* xv = (float*)(xch + 256);
+    const float sc = div_small_ints((float)my_cnt, (float)cand);
+    xs[lane] = sc;
+    WSYNC();
+    float log_sum = 0.0f;
+#pragma nounroll   // (unrolled eight times over, the loads of one step no longer fit the 64 registers of the fast class)
+    for (uint32_t t = 0; t < nT; t += 4) {
+        const u32x4 q = *(const u32x4*)((const uint32_t*)xs + t);
+        log_sum += __uint_as_float(q.x); log_sum += __uint_as_float(q.y); log_sum += __uint_as_float(q.z); log_sum += __uint_as_float(q.w);
+    }
+    const uint32_t pos_sig_hits = (uint32_t)popc64(bal(my_cnt > 0));
+    const uint32_t use_sig_hits = pos_sig_hits > 3 ? pos_sig_hits : nT;
+    log_avg = div_small_ints(log_sum, (float)use_sig_hits);
+    const float dv = log_avg - sc;
+    xv[lane] = (uint32_t)lane < nT && (pos_sig_hits > 3 ? my_cnt > 0 : true) ? dv * dv : 0.0f;
+    WSYNC();
+    float log_std = 0.0f;
+#pragma nounroll
+    for (uint32_t t = 0; t < nT; t += 4) {
+        const f32x4 q = *(const f32x4*)(xv + t);
+        log_std += q.x; log_std += q.y; log_std += q.z; log_std += q.w;
+    }
+    stdev1 = use_sig_hits > 1 ? sqrtf(div_small_ints(log_std, (float)(use_sig_hits - 1))) : 0.0f;
+    return sc;
+}
+// ... and its record: a call of slot call_tid (0: none, the LCA error) with the statistics above
+__device__ __forceinline__ void k4_wave_closed_record(CArgsK4* Ap, int lane, GAS uint64_t* out, uint8_t match, uint32_t call_tid, float call_score,
+                                                      uint32_t cand, float log_avg, float stdev1, int valid_kmers, uint32_t len, int bin_sel) {
+    lmat_read_result res;
+    res.status = LMAT_ST_CALL; res.match_type = match; res.cand_kmer_cnt = (uint16_t)cand; res.valid_kmers = valid_kmers;
+    res.read_len = (int)len; res.log_avg = log_avg; res.stdev = stdev1; res.cand_off = 0; res.n_cand = 0; res.bin_sel = bin_sel;
+    res.call_tid = call_tid ? ((const GAS uint32_t*)Ap->tb.tid32)[call_tid] : 0u;
+    res.call_score = call_score;
+    k4_wave_record(Ap, lane, out, res, call_tid);
+}
 // One lineage, decided in closed form.  `chain` = eligible slot | kept slots << 8 | 1 << 16 comes from a closure
 // that found ONE eligible id (slot sx0) and registered every one of its ancestors itself: slots 0 .. kept-1 are the ids the lists
 // kept, the slots behind them the ancestors of sx0 ("the chain"), each with sx0's count c0.  When every other kept id has a count
@@ -1166,28 +1205,8 @@ __device__ __forceinline__ bool k4_wave_chain(CArgsK4* Ap, int lane, uint32_t nT
     if ((~(bal(oi < rt) | bal(ro < ti)) & OTH) | (~(bal(ti < rt) & bal(ro <= oi)) & CH)) return false;
     // the chain reaches depth 0 (else :326-343 adds unregistered ancestors); no plasmid (:301-304), no screened PhiX id (:841-848)
     if (!(bal(dep == 0u) & CH) || bal((fl & badfl) != 0)) return false;
-    float* xs = (float*)xch;          // [64] scores by slot, [64] squared deviations: as k4_wave lays them out
-    float* xv = (float*)(xch + 256);
-    const float sc = div_small_ints((float)my_cnt, (float)cand);
-    xs[lane] = sc;
-    WSYNC();
-    float log_sum = 0.0f;
-    for (uint32_t t = 0; t < nT; t += 4) {
-        const u32x4 q = *(const u32x4*)((const uint32_t*)xs + t);
-        log_sum += __uint_as_float(q.x); log_sum += __uint_as_float(q.y); log_sum += __uint_as_float(q.z); log_sum += __uint_as_float(q.w);
-    }
-    const uint32_t pos_sig_hits = (uint32_t)popc64(bal(my_cnt > 0));
-    const uint32_t use_sig_hits = pos_sig_hits > 3 ? pos_sig_hits : nT;
-    const float log_avg = div_small_ints(log_sum, (float)use_sig_hits);
-    const float dv = log_avg - sc;
-    xv[lane] = (uint32_t)lane < nT && (pos_sig_hits > 3 ? my_cnt > 0 : true) ? dv * dv : 0.0f;
-    WSYNC();
-    float log_std = 0.0f;
-    for (uint32_t t = 0; t < nT; t += 4) {
-        const f32x4 q = *(const f32x4*)(xv + t);
-        log_std += q.x; log_std += q.y; log_std += q.z; log_std += q.w;
-    }
-    const float stdev1 = use_sig_hits > 1 ? sqrtf(div_small_ints(log_std, (float)(use_sig_hits - 1))) : 0.0f;
+    float log_avg, stdev1;
+    const float sc = k4_wave_stats(lane, nT, cand, my_cnt, xch, log_avg, stdev1);
     const float diff_thresh = stdev1 * Ap->prm.sdiff;
     const float s0 = __uint_as_float(rl(__float_as_uint(sc), (int)sx0));
     const float d = s0 - sc;
@@ -1209,12 +1228,87 @@ __device__ __forceinline__ bool k4_wave_chain(CArgsK4* Ap, int lane, uint32_t nT
             match = LMAT_MT_MULTI; call_tid = rl(my_id, (int)(k & 63u));
         }
     }
-    lmat_read_result res;
-    res.status = LMAT_ST_CALL; res.match_type = match; res.cand_kmer_cnt = (uint16_t)cand; res.valid_kmers = valid_kmers;
-    res.read_len = (int)len; res.log_avg = log_avg; res.stdev = stdev1; res.cand_off = 0; res.n_cand = 0; res.bin_sel = bin_sel;
-    res.call_tid = call_tid ? ((const GAS uint32_t*)Ap->tb.tid32)[call_tid] : 0u;
-    res.call_score = call_score;
-    k4_wave_record(Ap, lane, out, res, call_tid);
+    k4_wave_closed_record(Ap, lane, out, match, call_tid, call_score, cand, log_avg, stdev1, valid_kmers, len, bin_sel);
+    return true;
+}
+#if LMAT_ABLATE
+// ablation builds: why k4_wave_path turned a read away, counted across launches -- [0] offered, [1] decided, [2 ..] the first test
+// that failed, in the order of the code (scripts/path_share.py reads them through lmat_ablate_path_why)
+__device__ uint32_t g_path_why[16];
+#define PATH_WHY(i) do { if (lane == 0) atomicAdd(&g_path_why[i], 1u); } while (0)
+#else
+#define PATH_WHY(i) ((void)0)
+#endif
+// One dominant lineage, decided in closed form: the table need not come from a `lone` closure.  Of the closure
+// only the number of kept slots is asked (chain = kept << 8 | 1 << 17).  v = the kept slot with the largest count c0 (the highest
+// slot among equals), CH = the slots that are proper ancestors of v (by their Euler intervals, wherever they sit), OTH = the rest.
+// When every OTH count is below c0, every CH count at least c0, no OTH id lies below v, CH reaches depth 0 and nobody carries a
+// plasmid or a screened PhiX flag, findReadLabelVer2 (:284-419) collapses as it does for one lineage:
+//   * sorted by (count, depth) the array ends in exactly {v} u CH -- members of one root-to-leaf path: all depths differ, no two keys
+//     are equal, every pair is related --, so the lineage loop (:295-325) takes them all in whatever order and refuses the best
+//     OTH id, which is unrelated to v (neither above it: that would be CH, nor below it); lowest = v, highest at depth 0:
+//     nothing is added (:326-343);
+//   * cmpCompLineage (:264-282) walks the lineage deepest first for every OTH id j, best first, and meets v first, never an
+//     ancestor of j: d0 = s0 - s_j > diff_thresh ends the whole scan with no mark from j, and d0 does not fall along the scan,
+//     so the "close" ids (d0 <= diff_thresh) are exactly the ones walked, whatever std::sort made of equal keys.  The walk of a
+//     close j marks v and the CH entries that are no ancestors of j (the lower part of the path) and stops at the first ancestor
+//     -- unless an entry e on the way has s_e - s_j > diff_thresh (path counts may rise towards the root), which would end the
+//     scan there and make the marks depend on the order of equal keys: such a table is the general code's;
+//   * nothing marked: Direct, (v, s0).  Else the deepest CH entry g that is an ancestor of every close j is the first unmarked
+//     one: Multi, max_val = the largest score from v up to g (never below s_g: no Partial, :398-407); no such g: LCA error.
+// Every test is wave-uniform; a table that fails one is the general path's, unchanged.
+__device__ __forceinline__ bool k4_wave_path(CArgsK4* Ap, int lane, uint32_t nT, uint32_t cand, const u32x4 fz, uint32_t my_cnt,
+                                             uint32_t my_id, uint32_t dep, uint32_t fl, uint32_t chain, uint32_t* xch, GAS uint64_t* out,
+                                             int valid_kmers, uint32_t len, int bin_sel) {
+    const uint32_t nK = (chain >> 8) & 0x7Fu;
+    PATH_WHY(0);
+    if (nK - 1u >= nT) { PATH_WHY(2); return false; }   // 1 <= kept <= nT
+    const uint64_t am = below_mask_1_64((int)nT);
+    const uint32_t kv = wave_max_u32((uint32_t)lane < nK ? (my_cnt << 6) | (uint32_t)lane : 0u);   // counts are below 2^10 (k4_wave)
+    const uint32_t v = kv & 63u, c0 = kv >> 6;
+    const uint32_t ti = fz.z & 0xFFFFu, oi = fz.z >> 16;
+    const uint32_t riv = rl(fz.z, (int)v);
+    const uint32_t rt = riv & 0xFFFFu, ro = riv >> 16;
+    const uint64_t CH = bal(ti < rt) & bal(ro <= oi) & am, PATH = CH | (1ull << v), OTH = am & ~PATH;
+    if (!CH) { PATH_WHY(3); return false; }
+    // counts: the others below c0 (an equal count is a tie std::sort decides; a second kept slot at c0 is one), the path at c0 or above
+    if (~bal(my_cnt < c0) & OTH) { PATH_WHY(4); return false; }
+    if (~bal(my_cnt >= c0) & CH) { PATH_WHY(5); return false; }
+    // intervals: no other id below v (above it there is none: that is CH)
+    if (~(bal(oi < rt) | bal(ro < ti)) & OTH) { PATH_WHY(6); return false; }
+    // the path reaches depth 0 (else :326-343 adds ancestors); no plasmid (:301-304), no screened PhiX id (:841-848)
+    if (!(bal(dep == 0u) & CH)) { PATH_WHY(7); return false; }
+    const uint32_t badfl = (uint32_t)kFlagPlasmid | (Ap->prm.screen_phix ? (uint32_t)kFlagPhiX : 0u);
+    if (bal((fl & badfl) != 0)) { PATH_WHY(8); return false; }
+    float log_avg, stdev1;
+    const float sc = k4_wave_stats(lane, nT, cand, my_cnt, xch, log_avg, stdev1);
+    const float diff_thresh = stdev1 * Ap->prm.sdiff;
+    const float s0 = __uint_as_float(rl(__float_as_uint(sc), (int)v));
+    uint64_t close = bal(s0 - sc <= diff_thresh) & OTH;
+    uint8_t match = LMAT_MT_DIRECT;
+    uint32_t call_tid = rl(my_id, (int)v);
+    float call_score = s0;
+    if (close) {
+        uint64_t good = CH;   // path entries that are ancestors of every close id so far
+        do {
+            const int j = __builtin_ctzll(close);
+            close &= close - 1;
+            const uint32_t ivj = rl(fz.z, j);
+            const float sj = __uint_as_float(rl(__float_as_uint(sc), j));
+            const uint64_t anc = bal(ti < (ivj & 0xFFFFu)) & bal((ivj >> 16) <= oi);
+            if (bal(sc - sj > diff_thresh) & PATH & ~anc) { PATH_WHY(9); return false; }   // j's walk would end the scan part-way
+            good &= anc;
+        } while (close);
+        if (!good) {
+            match = LMAT_MT_LCA_ERROR; call_tid = 0; call_score = 0;
+        } else {  // the deepest of nested ancestors has the largest tin; the scores from v up to it are those of the tins at or above its own
+            const uint32_t k = wave_max_u32(lane_bit(good) ? (ti << 6) | (uint32_t)lane : 0u);
+            match = LMAT_MT_MULTI; call_tid = rl(my_id, (int)(k & 63u));
+            call_score = __uint_as_float(wave_max_u32(lane_bit(PATH) && ti >= (k >> 6) ? __float_as_uint(sc) : 0u));   // (scores are >= 0: ordered like their bits)
+        }
+    }
+    PATH_WHY(1);
+    k4_wave_closed_record(Ap, lane, out, match, call_tid, call_score, cand, log_avg, stdev1, valid_kmers, len, bin_sel);
     return true;
 }
 template <int THM, bool PLAIN = false>   // PLAIN: see classify_one
@@ -1247,12 +1341,22 @@ __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint
     if (bal(my_cnt > cand) | bal(dep > 0x7FFFu) | (hbias != 0.0f ? bal((fl & kFlagHuman) != 0) : 0ull)) return false;  // (a bias of 0 adds 0 * stdev: nothing)
     // one eligible id and its chain (the closure says so): the closed form, where the launch allows it (k4_static_of, bit 2: no -p,
     // no debug stop, LMAT_K4_CHAIN) and the table has its shape
-    if (LMAT_ABLATE && lane == 0) { G_ADD((GAS uint32_t*)Ap->cursor + kCurChainSeen, 1u); if (chain) G_ADD((GAS uint32_t*)Ap->cursor + kCurChainLone, 1u); }
-    if (chain && (PLAIN || (Ap->prm.k4_static & 4)) &&
+    if (LMAT_ABLATE && lane == 0) { G_ADD((GAS uint32_t*)Ap->cursor + kCurChainSeen, 1u); if (chain & 0x10000u) G_ADD((GAS uint32_t*)Ap->cursor + kCurChainLone, 1u); }
+    if ((chain & 0x10000u) && (PLAIN || (Ap->prm.k4_static & 4)) &&
         k4_wave_chain(Ap, lane, nT, cand, fz, my_cnt, my_id, dep, fl, chain, xch, out, valid_kmers, len, bin_sel)) {
         if (LMAT_ABLATE && lane == 0) G_ADD((GAS uint32_t*)Ap->cursor + kCurChainTaken, 1u);
         if (took_chain) *took_chain = 1u;
         return true;
+    }
+    // ... else one dominant lineage among others (k4_wave_path): the closure's word is the number of kept slots (bit 17); the
+    // launch allows it under the chain's conditions (k4_static_of, bit 3: LMAT_K4_PATH)
+    if ((chain & 0x20000u) && (PLAIN || (Ap->prm.k4_static & 8))) {
+        if (LMAT_ABLATE && lane == 0) G_ADD((GAS uint32_t*)Ap->cursor + kCurPathSeen, 1u);
+        if (k4_wave_path(Ap, lane, nT, cand, fz, my_cnt, my_id, dep, fl, chain, xch, out, valid_kmers, len, bin_sel)) {
+            if (LMAT_ABLATE && lane == 0) G_ADD((GAS uint32_t*)Ap->cursor + kCurPathTaken, 1u);
+            if (took_chain) *took_chain = 2u;
+            return true;
+        }
     }
     float* xs = (float*)xch;      // [64] scores by slot (stay: a registered ancestor's score is read from here)
     uint32_t* xk = xch + 64;      // [64] sort keys by array position; later the taxid of every sorted position
@@ -3114,7 +3218,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     WSYNC();
     STOP_AT(5, nT);
     RELANE();
-    uint32_t chain = 0;  // what the closure tells the decision step (k4_wave_chain): eligible slot | kept slots << 8 | 1 << 16, when `lone` held
+    uint32_t chain = 0;  // what the closure tells the decision step: kept slots << 8 | 1 << 17 when it finished (k4_wave_path), | eligible slot | 1 << 16 when `lone` held (k4_wave_chain)
     // representative strain per species (read_label.cpp:1144-1177): max leaf count, ties -> smallest taxid
     // (-s: the whole post pass :1143-1204 is skipped; the list records already hold the lineages)
     if constexpr (INK4) {
@@ -3329,10 +3433,11 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         // id -- its count is the id's own -- and steps (3a) .. (3c) have nothing else to find.  The usual read: strains of one
         // species, the representative one eligible.  (LMAT_CLOSURE_FAST, compile time.)
         const bool lone = one && !overflow && W > 0 && nT - nT_p1 == W && cand == nuniq;
+        if (!overflow) chain = 0x20000u | (nT_p1 << 8);   // the number of kept slots: all that k4_wave_path asks
         if (lone) {
             const uint32_t c0 = cnt[sx0];
             if ((uint32_t)lane >= nT_p1 && (uint32_t)lane < nT) cnt[lane] = (uint16_t)c0;
-            chain = 0x10000u | (nT_p1 << 8) | (uint32_t)sx0;
+            chain |= 0x10000u | (uint32_t)sx0;
             WSYNC();
         } else if (!overflow && W > 0) {
             const bool sl_act = (uint32_t)lane < nT;
@@ -3923,8 +4028,9 @@ __global__ __launch_bounds__(64) void k4_debug_counts_kernel(ClassifyArgs A, con
 // set up as classify_one leaves a read: lane s = registration slot s with the id's fact record in its registers, the ids in the
 // wave's taxid hash.  A table k4_wave declines (its preconditions, the heapsort turn of introsort, a lineage beyond 64 lanes,
 // two lineage entries of one depth) comes back with status 255: the general path's job.
-// `shape` (optional): per table what the closure would tell k4_wave -- eligible slot | kept slots << 8 | 1 << 16, or 0 --; `took` then
-// receives a byte per table: 1 where the closed form (k4_wave_chain) decided it.
+// `shape` (optional): per table what the closure would tell k4_wave -- eligible slot | kept slots << 8 | 1 << 16 for a `lone` one,
+// kept slots << 8 | 1 << 17 for any that finished, both, or 0 --; `took` then receives a byte per table: 1 where the closed form
+// for one lineage (k4_wave_chain) decided it, 2 where the one for a dominant lineage (k4_wave_path) did, 0 for the general code.
 __global__ __launch_bounds__(64) void k4_wave_debug_kernel(ClassifyArgs A, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ cnts,
                                                            const uint64_t* __restrict__ off, const uint32_t* __restrict__ cands, uint64_t n,
                                                            const uint32_t* __restrict__ shape, uint8_t* __restrict__ took) {
@@ -4235,15 +4341,16 @@ void launch_k4_end(const ClassifyArgs& a, hipStream_t join_stream, hipStream_t s
 }
 
 // Which decision paths the launch allows (bit 0: k4_wave, bit 1: k4_row_kernel, bit 2: k4_wave's closed form for one lineage,
-// k4_wave_chain), from what does not vary with the read.  The closed form leaves the candidate pairs of -p, which want every
-// candidate in sorted order, to the general code of k4_wave; LMAT_K4_CHAIN=0 turns it off.
+// k4_wave_chain, bit 3: its closed form for one dominant lineage, k4_wave_path), from what does not vary with the read.  The closed
+// forms leave the candidate pairs of -p, which want every candidate in sorted order, to the general code of k4_wave;
+// LMAT_K4_CHAIN=0 / LMAT_K4_PATH=0 turn them off (KernelParams::k4_chain, bits 0 and 1).
 static int k4_static_of(const ClassifyArgs& a) {
     const int stop = a.prm.stop_after;
     const bool base = !a.nm.active && a.tb.depth_consistent && !(a.cands && !a.prm.prn_all);
     const bool wave = base && (stop == 0 || (stop >= 30 && stop <= 34));
     const bool rows = base && a.prm.k4_row && stop == 0;
-    const bool chain = wave && stop == 0 && !a.cands && a.prm.k4_chain;
-    return (wave ? 1 : 0) | (rows ? 2 : 0) | (chain ? 4 : 0);
+    const bool closed = wave && stop == 0 && !a.cands;
+    return (wave ? 1 : 0) | (rows ? 2 : 0) | (closed && (a.prm.k4_chain & 1) ? 4 : 0) | (closed && (a.prm.k4_chain & 2) ? 8 : 0);
 }
 // The plain run (classify_one's PLAIN): every launch-wide value the variant has as a literal, checked here.  What stays a run-time
 // scalar in it -- the bucket width in its three forms, sdiff, the k-mer and score thresholds, the PhiX screen -- is not asked
@@ -4251,7 +4358,7 @@ static int k4_static_of(const ClassifyArgs& a) {
 static bool plain_launch(const ClassifyArgs& a, int k4_static) {
     static const bool on = !LMAT_ABLATE && (!getenv("LMAT_PLAIN") || atoi(getenv("LMAT_PLAIN")) != 0);
     return on && a.tb.k == 20 && a.tb.cpt.nb && a.tb.cpt.m == 17 && a.tb.cpt.lowbits == 2 && !a.tb.wide && !a.nm.active && !a.rand_max &&
-           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 5 && !a.cands && a.prm.hbias == 0.0f &&
+           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 13 && !a.cands && a.prm.hbias == 0.0f &&
            a.p_min == 0 && a.p_max == 0xFFFFFFFFu && !a.index && !a.count_ptr && a.tail_lpr == 4;
 }
 // The plain run over records of one geometry (classify_one's UNI): a.uniform is the host's word that every read of the launch has
@@ -4331,6 +4438,18 @@ void launch_k4_debug_counts(const ClassifyArgs& a, const uint32_t* idx, const ui
         k4_wave_debug_kernel<<<dim3((unsigned)g), dim3(64), 0, stream>>>(b, idx, cnts, off, cands, n, shape, took);
     } else k4_debug_counts_kernel<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream>>>(a, idx, cnts, off, cands, n);
 }
+
+#if LMAT_ABLATE
+}  // namespace lmat
+// ablation builds: k4_wave_path's reasons (g_path_why) since the last reset, read straight off the variant library (scripts/path_share.py)
+extern "C" int lmat_ablate_path_why(uint32_t* out16, int reset) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(lmat::g_path_why), 64) != hipSuccess) return -1;
+    if (reset) { const uint32_t z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lmat::g_path_why), z, 64) != hipSuccess) return -1; }
+    return 0;
+}
+namespace lmat {
+#endif
 
 void launch_tail(const ClassifyArgs& a, hipStream_t stream) {
     if (!a.tail_lpr || !a.count || a.count_ptr) return;

@@ -78,7 +78,9 @@ enum CursorWord {
     kCurK4Bail = 6,     // reads a K4 kernel could not hold after all
     kCurChainSeen = 11, // ablation builds only (-DLMAT_ABLATE=1): reads that met k4_wave's entry conditions,
     kCurChainLone = 12, // ... of them those whose closure found one eligible id and registered its whole chain,
-    kCurChainTaken = 13,// ... of them those the closed form decided (k4_wave_chain)
+    kCurChainTaken = 13,// ... of them those the closed form decided (k4_wave_chain),
+    kCurPathSeen = 14,  // ... of the rest those offered to the closed form for one dominant lineage (the closure finished),
+    kCurPathTaken = 1,  // ... of them those it decided (k4_wave_path)
     kCurBatchErr = 15, // error flags of a batch that keeps its own (the streamed boundary) instead of the sticky word
 };
 

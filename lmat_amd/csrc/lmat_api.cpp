@@ -100,7 +100,9 @@ static KernelParams kparams(const lmat_params& p) {
     k.k4_row = getenv("LMAT_K4_ROW") && atoi(getenv("LMAT_K4_ROW")) != 0;
     // LMAT_K4_CHAIN=0: reads of one lineage are decided by the general code of k4_wave, not by its closed form (k4_wave_chain).  The
     // plain-run variant has the closed form compiled in, so such a run takes the generic kernel: the off arm of the tests.
-    k.k4_chain = !(getenv("LMAT_K4_CHAIN") && atoi(getenv("LMAT_K4_CHAIN")) == 0);
+    k.k4_chain = !(getenv("LMAT_K4_CHAIN") && atoi(getenv("LMAT_K4_CHAIN")) == 0) ? 1 : 0;
+    // LMAT_K4_PATH=0: the same for reads of one dominant lineage among others (k4_wave_path): bit 1 of the field
+    if (!(getenv("LMAT_K4_PATH") && atoi(getenv("LMAT_K4_PATH")) == 0)) k.k4_chain |= 2;
     k.k4_static = 0;
     return k;
 }
@@ -2014,6 +2016,19 @@ int lmat_debug_decide_chain(lmat_ctx* c, const uint32_t* tids, const uint32_t* c
         shape[i] = kept[i] ? (0x10000u | (kept[i] << 8) | eligible[i]) : 0u;
     }
     return debug_decide_counts(c, tids, counts, off, cand, n, 1, &shape, with_cands, results, took);
+}
+// ... with the closure's word given as it is: shape[i] = kept << 8 | 1 << 17 (the closure finished: the closed form for one dominant
+// lineage, k4_wave_path, may decide the table), | eligible | 1 << 16 (`lone` held as well), or 0.  took[i] = 0 general code, 1 chain, 2 path.
+int lmat_debug_decide_shape(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand,
+                            const uint32_t* shape, uint64_t n, int with_cands, lmat_read_result* results, uint8_t* took) {
+    if (!c || !tids || !counts || !off || !cand || !shape || !results || !took) return LMAT_E_ARG;
+    std::vector<uint32_t> sh(shape, shape + n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t kept = (sh[i] >> 8) & 0xFFu, el = sh[i] & 0xFFu;
+        if ((sh[i] & ~0x3FFFFu) || kept > 64u || ((sh[i] & 0x10000u) && el >= kept) || (!(sh[i] & 0x10000u) && el) || (!(sh[i] & 0x30000u) && sh[i]))
+            return set_err(c, LMAT_E_ARG, "a shape word with kept slots above 64, an eligible slot that is not among them, or bits without their flag");
+    }
+    return debug_decide_counts(c, tids, counts, off, cand, n, 1, &sh, with_cands, results, took);
 }
 
 // Measurement hook: the per-launch counter block of the most recent launch (after lmat_sync), words as kernels.hpp's CursorWord
