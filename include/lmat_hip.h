@@ -578,7 +578,9 @@ int lmat_debug_decide_chain(lmat_ctx* ctx, const uint32_t* tids, const uint32_t*
 /* The same with the closure's word per table given as the classify kernel forms it: shape[i] = kept << 8 | 1 << 17 -- the closure
  * finished and kept that many slots: the closed form for ONE DOMINANT lineage among others may decide the table --, | eligible |
  * 1 << 16 when it also found one eligible id as above, or 0.  took[i] = 0 general code (or declined), 1 the closed form for one
- * lineage, 2 the one for a dominant lineage.  LMAT_K4_PATH=0 turns the latter off, LMAT_K4_CHAIN=0 the former. */
+ * lineage, 2 the one for a dominant lineage, 3 the one for TIED ids at the top, which is offered by | 1 << 18 (valid only beside bit
+ * 17; the classify kernel sets the two together; a word without it behaves as before).  LMAT_K4_TIE=0 turns the last off,
+ * LMAT_K4_PATH=0 the second, LMAT_K4_CHAIN=0 the first. */
 int lmat_debug_decide_shape(lmat_ctx* ctx, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand,
                             const uint32_t* shape, uint64_t n, int with_cands, lmat_read_result* results, uint8_t* took);
 

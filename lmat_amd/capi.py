@@ -1066,7 +1066,8 @@ class Engine:
     def debug_decide_shape(self, tids, counts, off, cand, shape, with_cands=False):
         """debug_decide_counts on the wave with the closure's word per table as the classify kernel forms it: shape[i] = kept << 8 |
         1 << 17 (the closure finished), | eligible | 1 << 16 (it found one eligible id and registered its chain), or 0 -> (results,
-        took): took[i] = 0 where the general code decided table i, 1 the closed form for one lineage, 2 the one for a dominant lineage."""
+        took): took[i] = 0 where the general code decided table i, 1 the closed form for one lineage, 2 the one for a dominant lineage,
+        3 the one for tied ids at the top (offered by | 1 << 18 beside bit 17)."""
         tids = np.ascontiguousarray(tids, dtype=np.uint32)
         counts = np.ascontiguousarray(counts, dtype=np.uint32)
         off = np.ascontiguousarray(off, dtype=np.uint64)

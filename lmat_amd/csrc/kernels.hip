@@ -1311,6 +1311,121 @@ __device__ __forceinline__ bool k4_wave_path(CArgsK4* Ap, int lane, uint32_t nT,
     k4_wave_closed_record(Ap, lane, out, match, call_tid, call_score, cand, log_avg, stdev1, valid_kmers, len, bin_sel);
     return true;
 }
+#if LMAT_ABLATE
+// ablation builds: what became of the reads offered to k4_wave_tie, counted across launches -- [0] offered, [1] decided, [2 .. 15] the
+// first test that failed, in the order of the code, [16] / [17] tied ids of one depth with / without an ancestor counting above c0
+// (scripts/tie_share.py reads them through lmat_ablate_tie_why)
+__device__ uint32_t g_tie_why[32];
+#define TIE_WHY(i) do { if (lane == 0) atomicAdd(&g_tie_why[i], 1u); } while (0)
+#else
+#define TIE_WHY(i) ((void)0)
+#endif
+// Tied ids at the top, decided in closed form: what k4_wave_path turns away for "another id with a count >= c0".
+// Of the closure the number of kept slots is asked, as there (chain = kept << 8 | 1 << 17 | 1 << 18).  c0 = the largest kept count,
+// TOP = the kept slots at c0: two or more, all of one depth.  By the Euler intervals, wherever the slots sit: COMMON = the proper
+// ancestors of every TOP id, PRIVATE = those of some but not all, REST = the others.  Asked: every ancestor of a TOP id is
+// registered (as many slots above it as its path has entries); REST counts below c0, PRIVATE counts at c0, COMMON counts at c0 or
+// above and not falling towards the root; no REST id below a TOP id; COMMON reaches depth 0 and holds no kept slot (its deepest is
+// one the closure registered); no plasmid or screened PhiX flag; a threshold that is not negative.  Then findReadLabelVer2 (:284-419) collapses:
+//   * sorted by (count, depth) the array ends ... TOP in whatever order std::sort left | GT, the slots above c0: a part of COMMON, so
+//     members of one path, every pair related, all accepted.  The next is a TOP id X (nothing at c0 is deeper: PRIVATE and COMMON
+//     lie above TOP ids), accepted as well; the one after it is a TOP id of X's depth: it misfits and ends the lineage (:225-262);
+//   * GT not empty: lowest = X, highest = the shallowest of GT, which is at depth 0 (counts do not fall towards the root, so the
+//     ancestors of a GT slot are GT; all are registered): nothing is added (:326-343), the lineage is X and GT.  GT empty: highest =
+//     X, and :326-343 adds every ancestor of X with its own score -- X's PRIVATE ancestors and all of COMMON, each at c0;
+//   * competitors (:355-362, cmpCompLineage :264-282), best first: the other TOP ids, difference 0 <= diff_thresh, mark X and X's
+//     PRIVATE ancestors that are not their own (every one of those is marked: some TOP id is not below it, and nothing on that id's
+//     way up to it is its ancestor or differs from s0) and stop at their first ancestor, in COMMON at the latest; PRIVATE and
+//     COMMON slots at c0 do the same and no more.  REST ids come by falling count: d = s0 - s_j at the entry X (never an ancestor
+//     of j), so the ids walked are the "close" ones (d <= diff_thresh) and the first other ends the scan with no mark; a close j
+//     marks the COMMON entries of the lineage that are no ancestors of it -- unless one of them has s_e - s_j > diff_thresh, which
+//     ends the scan part-way: the general code's;
+//   * X is marked: never Direct.  The first unmarked entry g is the deepest entry of LIN (GT, or all of COMMON where GT is empty)
+//     that is an ancestor of every close id: Multi, max_val = the largest score from X up to g = s_g (counts do not fall towards
+//     the root; g is registered and max_val is not below s_g: never Partial, :398-407); no such g: LCA error.
+// None of it depends on which TOP id X is: X and its PRIVATE ancestors are marked whichever it is, LIN and the marks on it are
+// defined by TOP as a set.  Every test is wave-uniform; a table that fails one is the general code's, unchanged.
+__device__ __forceinline__ bool k4_wave_tie(CArgsK4* Ap, int lane, uint32_t nT, uint32_t cand, const u32x4 fz, uint32_t my_cnt,
+                                            uint32_t my_id, uint32_t dep, uint32_t fl, uint32_t chain, uint32_t* xch, GAS uint64_t* out,
+                                            int valid_kmers, uint32_t len, int bin_sel) {
+    const uint32_t nK = (chain >> 8) & 0x7Fu;
+    TIE_WHY(0);
+    if (nK < 2u || nK >= nT) { TIE_WHY(2); return false; }   // two tied ids among the kept slots, a registered ancestor behind them
+    const uint64_t am = below_mask_1_64((int)nT), KEPT = below_mask_1_64((int)nK);
+    const uint32_t ti = fz.z & 0xFFFFu, oi = fz.z >> 16;
+    // the largest kept count, and of the kept slots that have it the one with the largest tin (counts are below 2^10: k4_wave)
+    const uint32_t kv = wave_max_u32((uint32_t)lane < nK ? (my_cnt << 22) | (ti << 6) | (uint32_t)lane : 0u);
+    const uint32_t c0 = kv >> 22, tmax = (kv >> 6) & 0xFFFFu, v = kv & 63u;
+    const uint64_t EQ = bal(my_cnt == c0), GT = bal(my_cnt > c0) & am, TOP = EQ & KEPT;
+    if (!(TOP & (TOP - 1)) || c0 == 0u) { TIE_WHY(3); return false; }   // one id at the top: whatever turned k4_wave_path away, it is no tie
+    const uint32_t D = rl(dep, (int)v);
+    if (~bal(dep == D) & TOP) { TIE_WHY(4); return false; }   // tied ids of unequal depth: the deeper sorts last
+    // above every TOP id: above the one with the smallest tin and the one with the largest
+    const uint32_t tmin = 0xFFFFu - wave_max_u32(lane_bit(TOP) ? 0xFFFFu - ti : 0u);
+    const uint64_t COMMON = bal(ti < tmin) & bal(tmax <= oi) & am;
+    // the other slots that may lie above a TOP id -- depths grow along every branch (k4_static_of) --, one by one: the TOP ids below
+    // each.  Per TOP id the slots above it are then as many as its path has entries (word 1 of a kept id's fact record), or :326-343
+    // could add an ancestor that has no slot.
+    uint64_t PRIVATE = 0;
+    uint32_t nabove = (uint32_t)popc64(COMMON);
+    for (uint64_t t = bal(dep < D) & am & ~COMMON; t; t &= t - 1) {
+        const int j = __builtin_ctzll(t);
+        const uint32_t ivj = rl(fz.z, j);
+        const uint64_t under = bal((ivj & 0xFFFFu) < ti) & bal(ti <= (ivj >> 16)) & TOP;
+        if (under) PRIVATE |= 1ull << j;
+        nabove += lane_bit(under) ? 1u : 0u;
+    }
+    if (LMAT_ABLATE) TIE_WHY(GT & (COMMON | PRIVATE) ? 16 : 17);
+    if (bal(nabove != (fz.y & 0xFFFFu)) & TOP) { TIE_WHY(5); return false; }
+    if (!COMMON) { TIE_WHY(6); return false; }
+    const uint64_t REST = am & ~COMMON & ~PRIVATE & ~TOP;
+    if (GT & ~COMMON) { TIE_WHY(7); return false; }
+    if (~EQ & PRIVATE) { TIE_WHY(8); return false; }
+    if (EQ & REST) { TIE_WHY(9); return false; }
+    if (~(GT | EQ) & COMMON) { TIE_WHY(10); return false; }
+    // (COMMON's slots are all the closure's: a kept one would count c0 at most, so c0, and be a TOP id of another depth)
+    if (GT) {   // along COMMON the counts do not fall towards the root: nothing above a GT slot counts less
+        const uint32_t key = (my_cnt << 16) | ti;
+        for (uint64_t t = GT; t; t &= t - 1) {
+            const uint32_t kj = rl(key, __builtin_ctzll(t));
+            if (bal(ti < (kj & 0xFFFFu)) & bal(my_cnt < (kj >> 16)) & COMMON) { TIE_WHY(10); return false; }
+        }
+    }
+    if (COMMON & KEPT) { TIE_WHY(11); return false; }
+    if (!(bal(dep == 0u) & COMMON)) { TIE_WHY(12); return false; }
+    const uint32_t badfl = (uint32_t)kFlagPlasmid | (Ap->prm.screen_phix ? (uint32_t)kFlagPhiX : 0u);
+    if (bal((fl & badfl) != 0)) { TIE_WHY(13); return false; }
+    for (uint64_t t = bal(dep > D) & REST; t; t &= t - 1) {   // no REST id below a TOP id
+        const uint32_t ivj = rl(fz.z, __builtin_ctzll(t));
+        if (bal(ti < (ivj & 0xFFFFu)) & bal((ivj >> 16) <= oi) & TOP) { TIE_WHY(14); return false; }
+    }
+    float log_avg, stdev1;
+    const float sc = k4_wave_stats(lane, nT, cand, my_cnt, xch, log_avg, stdev1);
+    const float diff_thresh = stdev1 * Ap->prm.sdiff;
+    if (!(diff_thresh >= 0.0f)) { TIE_WHY(15); return false; }   // (a tied id's difference of 0 must mark)
+    const float s0 = __uint_as_float(rl(__float_as_uint(sc), (int)v));
+    const uint64_t LIN = GT ? GT : COMMON;
+    uint64_t close = bal(s0 - sc <= diff_thresh) & REST, good = LIN;
+    while (close) {
+        const int j = __builtin_ctzll(close);
+        close &= close - 1;
+        const uint32_t ivj = rl(fz.z, j);
+        const float sj = __uint_as_float(rl(__float_as_uint(sc), j));
+        const uint64_t anc = bal(ti < (ivj & 0xFFFFu)) & bal((ivj >> 16) <= oi);
+        if (bal(sc - sj > diff_thresh) & LIN & ~anc) { TIE_WHY(15); return false; }   // j's walk would end the scan part-way
+        good &= anc;
+    }
+    uint8_t match = LMAT_MT_LCA_ERROR;
+    uint32_t call_tid = 0;
+    float call_score = 0;
+    if (good) {  // the deepest of nested ancestors has the largest tin; its score is the largest from X up to it
+        const uint32_t k = wave_max_u32(lane_bit(good) ? (ti << 6) | (uint32_t)lane : 0u) & 63u;
+        match = LMAT_MT_MULTI; call_tid = rl(my_id, (int)k); call_score = __uint_as_float(rl(__float_as_uint(sc), (int)k));
+    }
+    TIE_WHY(1);
+    k4_wave_closed_record(Ap, lane, out, match, call_tid, call_score, cand, log_avg, stdev1, valid_kmers, len, bin_sel);
+    return true;
+}
 template <int THM, bool PLAIN = false>   // PLAIN: see classify_one
 __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint32_t cand, const u32x4 fz, uint32_t my_cnt,
                                         uint32_t my_id, const unsigned int* hent, uint32_t* xch, GAS uint64_t* out,
@@ -1355,6 +1470,19 @@ __device__ __forceinline__ bool k4_wave(CArgsK4* Ap, int lane, uint32_t nT, uint
         if (k4_wave_path(Ap, lane, nT, cand, fz, my_cnt, my_id, dep, fl, chain, xch, out, valid_kmers, len, bin_sel)) {
             if (LMAT_ABLATE && lane == 0) G_ADD((GAS uint32_t*)Ap->cursor + kCurPathTaken, 1u);
             if (took_chain) *took_chain = 2u;
+            return true;
+        }
+    }
+    // ... else tied ids at the top (k4_wave_tie): offered by bit 18 of the closure's word, allowed by the launch under the same
+    // conditions (k4_static_of, bit 4: LMAT_K4_TIE)
+    if ((chain & 0x40000u) && (PLAIN || (Ap->prm.k4_static & 16))) {
+        if (LMAT_ABLATE && stop == 35) {   // timing experiment: the reads with tied kept ids of one depth end here
+            const uint32_t nK = (chain >> 8) & 0x7Fu;
+            const uint32_t kv = wave_max_u32((uint32_t)lane < nK ? (my_cnt << 6) | (uint32_t)lane : 0u);
+            const uint64_t TOP = bal(my_cnt == (kv >> 6)) & below_mask_1_64((int)(nK ? nK : 1u));
+            if (nK >= 2u && (TOP & (TOP - 1)) && !(~bal(dep == rl(dep, (int)(kv & 63u))) & TOP)) return placeholder();
+        } else if (k4_wave_tie(Ap, lane, nT, cand, fz, my_cnt, my_id, dep, fl, chain, xch, out, valid_kmers, len, bin_sel)) {
+            if (took_chain) *took_chain = 3u;
             return true;
         }
     }
@@ -3218,7 +3346,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     WSYNC();
     STOP_AT(5, nT);
     RELANE();
-    uint32_t chain = 0;  // what the closure tells the decision step: kept slots << 8 | 1 << 17 when it finished (k4_wave_path), | eligible slot | 1 << 16 when `lone` held (k4_wave_chain)
+    uint32_t chain = 0;  // what the closure tells the decision step: kept slots << 8 | 1 << 17 | 1 << 18 when it finished (k4_wave_path, k4_wave_tie), | eligible slot | 1 << 16 when `lone` held (k4_wave_chain)
     // representative strain per species (read_label.cpp:1144-1177): max leaf count, ties -> smallest taxid
     // (-s: the whole post pass :1143-1204 is skipped; the list records already hold the lineages)
     if constexpr (INK4) {
@@ -3433,7 +3561,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         // id -- its count is the id's own -- and steps (3a) .. (3c) have nothing else to find.  The usual read: strains of one
         // species, the representative one eligible.  (LMAT_CLOSURE_FAST, compile time.)
         const bool lone = one && !overflow && W > 0 && nT - nT_p1 == W && cand == nuniq;
-        if (!overflow) chain = 0x20000u | (nT_p1 << 8);   // the number of kept slots: all that k4_wave_path asks
+        if (!overflow) chain = 0x60000u | (nT_p1 << 8);   // the number of kept slots: all that k4_wave_path (bit 17) and k4_wave_tie (bit 18) ask
         if (lone) {
             const uint32_t c0 = cnt[sx0];
             if ((uint32_t)lane >= nT_p1 && (uint32_t)lane < nT) cnt[lane] = (uint16_t)c0;
@@ -4341,16 +4469,18 @@ void launch_k4_end(const ClassifyArgs& a, hipStream_t join_stream, hipStream_t s
 }
 
 // Which decision paths the launch allows (bit 0: k4_wave, bit 1: k4_row_kernel, bit 2: k4_wave's closed form for one lineage,
-// k4_wave_chain, bit 3: its closed form for one dominant lineage, k4_wave_path), from what does not vary with the read.  The closed
-// forms leave the candidate pairs of -p, which want every candidate in sorted order, to the general code of k4_wave;
-// LMAT_K4_CHAIN=0 / LMAT_K4_PATH=0 turn them off (KernelParams::k4_chain, bits 0 and 1).
+// k4_wave_chain, bit 3: its closed form for one dominant lineage, k4_wave_path, bit 4: the one for tied ids at the top, k4_wave_tie),
+// from what does not vary with the read.  The closed forms leave the candidate pairs of -p, which want every candidate in sorted
+// order, to the general code of k4_wave; LMAT_K4_CHAIN=0 / LMAT_K4_PATH=0 / LMAT_K4_TIE=0 turn them off (KernelParams::k4_chain,
+// bits 0, 1 and 2).  (Stop 35, ablation builds: the timing experiment of k4_wave that needs the closed forms in place.)
 static int k4_static_of(const ClassifyArgs& a) {
     const int stop = a.prm.stop_after;
     const bool base = !a.nm.active && a.tb.depth_consistent && !(a.cands && !a.prm.prn_all);
-    const bool wave = base && (stop == 0 || (stop >= 30 && stop <= 34));
+    const bool wave = base && (stop == 0 || (stop >= 30 && stop <= 35));
     const bool rows = base && a.prm.k4_row && stop == 0;
-    const bool closed = wave && stop == 0 && !a.cands;
-    return (wave ? 1 : 0) | (rows ? 2 : 0) | (closed && (a.prm.k4_chain & 1) ? 4 : 0) | (closed && (a.prm.k4_chain & 2) ? 8 : 0);
+    const bool closed = wave && (stop == 0 || stop == 35) && !a.cands;
+    return (wave ? 1 : 0) | (rows ? 2 : 0) | (closed && (a.prm.k4_chain & 1) ? 4 : 0) | (closed && (a.prm.k4_chain & 2) ? 8 : 0) |
+           (closed && (a.prm.k4_chain & 4) ? 16 : 0);
 }
 // The plain run (classify_one's PLAIN): every launch-wide value the variant has as a literal, checked here.  What stays a run-time
 // scalar in it -- the bucket width in its three forms, sdiff, the k-mer and score thresholds, the PhiX screen -- is not asked
@@ -4358,7 +4488,7 @@ static int k4_static_of(const ClassifyArgs& a) {
 static bool plain_launch(const ClassifyArgs& a, int k4_static) {
     static const bool on = !LMAT_ABLATE && (!getenv("LMAT_PLAIN") || atoi(getenv("LMAT_PLAIN")) != 0);
     return on && a.tb.k == 20 && a.tb.cpt.nb && a.tb.cpt.m == 17 && a.tb.cpt.lowbits == 2 && !a.tb.wide && !a.nm.active && !a.rand_max &&
-           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 13 && !a.cands && a.prm.hbias == 0.0f &&
+           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 29 && !a.cands && a.prm.hbias == 0.0f &&
            a.p_min == 0 && a.p_max == 0xFFFFFFFFu && !a.index && !a.count_ptr && a.tail_lpr == 4;
 }
 // The plain run over records of one geometry (classify_one's UNI): a.uniform is the host's word that every read of the launch has
@@ -4442,6 +4572,12 @@ void launch_k4_debug_counts(const ClassifyArgs& a, const uint32_t* idx, const ui
 #if LMAT_ABLATE
 }  // namespace lmat
 // ablation builds: k4_wave_path's reasons (g_path_why) since the last reset, read straight off the variant library (scripts/path_share.py)
+extern "C" int lmat_ablate_tie_why(uint32_t* out32, int reset) {   // ... and k4_wave_tie's (g_tie_why; scripts/tie_share.py)
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(lmat::g_tie_why), 128) != hipSuccess) return -1;
+    if (reset) { const uint32_t z[32] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lmat::g_tie_why), z, 128) != hipSuccess) return -1; }
+    return 0;
+}
 extern "C" int lmat_ablate_path_why(uint32_t* out16, int reset) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(lmat::g_path_why), 64) != hipSuccess) return -1;

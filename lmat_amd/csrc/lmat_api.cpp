@@ -103,6 +103,8 @@ static KernelParams kparams(const lmat_params& p) {
     k.k4_chain = !(getenv("LMAT_K4_CHAIN") && atoi(getenv("LMAT_K4_CHAIN")) == 0) ? 1 : 0;
     // LMAT_K4_PATH=0: the same for reads of one dominant lineage among others (k4_wave_path): bit 1 of the field
     if (!(getenv("LMAT_K4_PATH") && atoi(getenv("LMAT_K4_PATH")) == 0)) k.k4_chain |= 2;
+    // LMAT_K4_TIE=0: the same for reads with tied ids at the top (k4_wave_tie): bit 2
+    if (!(getenv("LMAT_K4_TIE") && atoi(getenv("LMAT_K4_TIE")) == 0)) k.k4_chain |= 4;
     k.k4_static = 0;
     return k;
 }
@@ -2018,14 +2020,16 @@ int lmat_debug_decide_chain(lmat_ctx* c, const uint32_t* tids, const uint32_t* c
     return debug_decide_counts(c, tids, counts, off, cand, n, 1, &shape, with_cands, results, took);
 }
 // ... with the closure's word given as it is: shape[i] = kept << 8 | 1 << 17 (the closure finished: the closed form for one dominant
-// lineage, k4_wave_path, may decide the table), | eligible | 1 << 16 (`lone` held as well), or 0.  took[i] = 0 general code, 1 chain, 2 path.
+// lineage, k4_wave_path, may decide the table), | 1 << 18 (so may the one for tied ids at the top, k4_wave_tie: classify_one sets both
+// bits together), | eligible | 1 << 16 (`lone` held as well), or 0.  took[i] = 0 general code, 1 chain, 2 path, 3 tie.
 int lmat_debug_decide_shape(lmat_ctx* c, const uint32_t* tids, const uint32_t* counts, const uint64_t* off, const uint32_t* cand,
                             const uint32_t* shape, uint64_t n, int with_cands, lmat_read_result* results, uint8_t* took) {
     if (!c || !tids || !counts || !off || !cand || !shape || !results || !took) return LMAT_E_ARG;
     std::vector<uint32_t> sh(shape, shape + n);
     for (uint64_t i = 0; i < n; ++i) {
         const uint32_t kept = (sh[i] >> 8) & 0xFFu, el = sh[i] & 0xFFu;
-        if ((sh[i] & ~0x3FFFFu) || kept > 64u || ((sh[i] & 0x10000u) && el >= kept) || (!(sh[i] & 0x10000u) && el) || (!(sh[i] & 0x30000u) && sh[i]))
+        if ((sh[i] & ~0x7FFFFu) || kept > 64u || ((sh[i] & 0x10000u) && el >= kept) || (!(sh[i] & 0x10000u) && el) || (!(sh[i] & 0x30000u) && sh[i]) ||
+            ((sh[i] & 0x40000u) && !(sh[i] & 0x20000u)))
             return set_err(c, LMAT_E_ARG, "a shape word with kept slots above 64, an eligible slot that is not among them, or bits without their flag");
     }
     return debug_decide_counts(c, tids, counts, off, cand, n, 1, &sh, with_cands, results, took);
