@@ -222,6 +222,12 @@ int lmat_nullmodel_clear(lmat_ctx* ctx);
  * Replaces the (read,hdr) queue hand-off of main() (read_label.cpp:1716-1746):
  * bases = concatenated ASCII, off[n+1] byte offsets. */
 int lmat_reads_upload(lmat_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint64_t n, lmat_reads** out);
+/* Paired-end reads: read i of the result is mate i of bases1/off1, an 'N', mate i of bases2/off2 -- the record upstream's
+ * bin/merge_fastq_reads_with_N_separator.pl makes on disk -- joined on the device while the reads are packed.  An ordinary
+ * lmat_reads of n_pairs reads in every respect (classify, download: the image of a pair is mate1 N mate2).  Either mate
+ * may be empty; offsets need not start at 0. */
+int lmat_reads_upload_pairs(lmat_ctx* ctx, const uint8_t* bases1, const uint64_t* off1, const uint8_t* bases2,
+                            const uint64_t* off2, uint64_t n_pairs, lmat_reads** out);
 int lmat_reads_synth(lmat_ctx* ctx, uint64_t n, const uint32_t* lengths, uint32_t n_lengths, uint64_t seed,
                      lmat_reads** out);
 int lmat_reads_download_ascii(lmat_ctx* ctx, const lmat_reads* r, uint64_t first, uint64_t count, uint8_t* bases,
@@ -283,7 +289,17 @@ int lmat_stream_submit(lmat_stream* st, uint64_t n_reads, uint64_t tag);
  * lmat_host_alloc; off need not start at 0), which the device reads directly: no copy into the slot.  The buffer must
  * stay untouched until lmat_stream_next has returned this batch. */
 int lmat_stream_submit_from(lmat_stream* st, const uint8_t* bases, const uint64_t* off, uint64_t n_reads, uint64_t tag);
-/* Page-locked host memory for buffers handed to lmat_stream_submit_from. */
+/* Paired-end batches (joined on the device as by lmat_reads_upload_pairs).  A batch of n_pairs gives n_pairs results whose
+ * read_len is l1 + 1 + l2.  It counts 2 x n_pairs reads against max_reads and sum(l1 + l2) + n_pairs bases against
+ * max_bases (LMAT_E_ARG above either, the slot goes back untouched); a joined length above what one read may have is
+ * refused like a read of that length.
+ *   submit_pairs       the acquired slot holds 2 x n_pairs reads, mates 1 and 2 in turn, under off[2 x n_pairs + 1]
+ *   submit_pairs_from  mates 1 are off1[0..n_pairs] inside the caller's own pinned buffer bases1, mates 2 off2[0..n_pairs]
+ *                      inside bases2 (one buffer or two), with the rules of lmat_stream_submit_from */
+int lmat_stream_submit_pairs(lmat_stream* st, uint64_t n_pairs, uint64_t tag);
+int lmat_stream_submit_pairs_from(lmat_stream* st, const uint8_t* bases1, const uint64_t* off1, const uint8_t* bases2,
+                                  const uint64_t* off2, uint64_t n_pairs, uint64_t tag);
+/* Page-locked host memory for buffers handed to lmat_stream_submit_from / lmat_stream_submit_pairs_from. */
 int lmat_host_alloc(uint64_t bytes, void** out);
 void lmat_host_free(void* p);
 int lmat_stream_next(lmat_stream* st, const lmat_read_result** results, const lmat_cand** cands, uint64_t* n_reads,

@@ -212,6 +212,9 @@ def load_library(path: str | None = None):
         "lmat_genebuild_create": (i32, [vp, i32, P(vp)]),
         "lmat_genedb_build_from_genes": (i32, [vp, vp, u64]),
         "lmat_table_unaddress": (i32, [i32, u64, u32, u32, P(u64)]),
+        "lmat_reads_upload_pairs": (i32, [vp, vp, vp, vp, vp, u64, P(vp)]),
+        "lmat_stream_submit_pairs": (i32, [vp, u64, u64]),
+        "lmat_stream_submit_pairs_from": (i32, [vp, vp, vp, vp, vp, u64, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -243,7 +246,8 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_export_create", "lmat_export_destroy", "lmat_export_error", "lmat_export_set_options", "lmat_export_run", "lmat_export_fetch",
             "lmat_export_taxid_counts", "lmat_build_add_db", "lmat_table_unaddress",
             "lmat_genebuild_create", "lmat_genedb_build_from_genes",
-            "lmat_debug_stream_stats", "lmat_debug_reads_words"]
+            "lmat_debug_stream_stats", "lmat_debug_reads_words",
+            "lmat_reads_upload_pairs", "lmat_stream_submit_pairs", "lmat_stream_submit_pairs_from"]
 
 
 def _ptr(a):
@@ -373,6 +377,29 @@ class Stream:
         pb, po = C.c_void_p(), C.c_void_p()
         self.eng._chk(self.lib.lmat_stream_acquire(self.h, C.byref(pb), C.byref(po)))
         self.eng._chk(self.lib.lmat_stream_submit_from(self.h, bases_ptr, off.ctypes.data, n, tag))
+        self.in_flight += 1
+
+    def submit_pairs(self, blob, off, tag=0):
+        """Paired-end: blob/off hold 2n reads, mates 1 and 2 in turn (off: uint64[2n + 1]); copied into the slot, joined on the
+        device into n reads mate1 N mate2."""
+        n2 = off.size - 1
+        if n2 % 2:   # (before a slot is taken: an acquired slot has to be submitted)
+            raise ValueError("an interleaved batch holds an even number of reads")
+        pb, po = C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.lib.lmat_stream_acquire(self.h, C.byref(pb), C.byref(po)))
+        # (a batch above the stream's limits is for the engine to refuse, from its count or its offsets: nothing is copied past a slot's end)
+        if n2 <= self.max_reads:
+            C.memmove(po, off.ctypes.data, (n2 + 1) * 8)
+            if int(off[-1]) <= self.max_bases:
+                C.memmove(pb, blob.ctypes.data, int(off[-1]))
+        self.eng._chk(self.lib.lmat_stream_submit_pairs(self.h, n2 // 2, tag))
+        self.in_flight += 1
+
+    def submit_pairs_pinned(self, ptr1, off1, ptr2, off2, n, tag=0):
+        """Paired-end: mates 1 are off1[0..n] in the caller's pinned buffer at ptr1, mates 2 off2[0..n] at ptr2.  No host copy."""
+        pb, po = C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.lib.lmat_stream_acquire(self.h, C.byref(pb), C.byref(po)))
+        self.eng._chk(self.lib.lmat_stream_submit_pairs_from(self.h, ptr1, off1.ctypes.data, ptr2, off2.ctypes.data, n, tag))
         self.in_flight += 1
 
     def next_nocopy(self):
@@ -878,6 +905,18 @@ class Engine:
         off = np.ascontiguousarray(off, dtype=np.uint64)
         h = C.c_void_p()
         self._chk(self.lib.lmat_reads_upload(self.ctx, _ptr(blob), _ptr(off), off.size - 1, C.byref(h)))
+        return Reads(self, h)
+
+    def upload_read_pairs(self, mates1, mates2) -> Reads:
+        """Paired-end reads, each (uint8 blob, uint64 offsets): read i of the result is mate i of the first, an N, mate i of the
+        second, joined on the device."""
+        (blob1, off1), (blob2, off2) = mates1, mates2
+        blob1, blob2 = np.ascontiguousarray(blob1, dtype=np.uint8), np.ascontiguousarray(blob2, dtype=np.uint8)
+        off1, off2 = np.ascontiguousarray(off1, dtype=np.uint64), np.ascontiguousarray(off2, dtype=np.uint64)
+        if off1.size != off2.size:
+            raise ValueError("as many mates 1 as mates 2")
+        h = C.c_void_p()
+        self._chk(self.lib.lmat_reads_upload_pairs(self.ctx, _ptr(blob1), _ptr(off1), _ptr(blob2), _ptr(off2), off1.size - 1, C.byref(h)))
         return Reads(self, h)
 
     def synth_reads(self, n, lengths=(150,), seed=3003) -> Reads:

@@ -90,6 +90,12 @@ enum { kErrTidOverflow = 1, kErrReadTooLong = 2, kErrCandOverflow = 4, kErrLinea
 void launch_fill_offsets(uint64_t* off, uint64_t* rec_off, uint64_t n, uint32_t len, hipStream_t stream);  // off[i] = i * len, rec_off[i] = i * rec_words(len), i = 0..n
 void launch_pack_reads(const uint8_t* bases, const uint64_t* off, const uint64_t* rec_off, uint32_t* words, uint64_t n,
                        hipStream_t stream);
+// pairs.hip: the record of pair r is pack_reads' record of  mate1 'N' mate2;  mates at off1[r * stride] .. off1[r * stride + 1] and
+// off2[r * stride] .. off2[r * stride + 1] of `bases` (interleaved offsets: off2 = off1 + 1, stride 2; two blocks: stride 1)
+void launch_pack_pairs(const uint8_t* bases, const uint64_t* off1, const uint64_t* off2, uint32_t stride, const uint64_t* rec_off, uint32_t* words,
+                       uint64_t n, hipStream_t stream);
+// ... for n pairs of l1 + l2 bases laid out from 0: those offsets (2n + 1 of them; two_block: off[0..n] mates 1, off[n..2n] mates 2) and rec_off[0..n]
+void launch_fill_pair_offsets(uint64_t* off, uint64_t* rec_off, uint64_t n, uint32_t l1, uint32_t l2, bool two_block, hipStream_t stream);
 void launch_insert_pairs(const DeviceTables& tb, const uint64_t* kmers, const uint32_t* payload, uint64_t n,
                          uint32_t* fail, hipStream_t stream);
 void launch_synth_db(const DeviceTables& tb, const SynthGeo& g, int k, const uint16_t* strain_idx, const uint32_t* list_payload,

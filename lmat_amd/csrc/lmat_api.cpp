@@ -1286,6 +1286,57 @@ int lmat_reads_upload(lmat_ctx* c, const uint8_t* bases, const uint64_t* off, ui
     return LMAT_OK;
 }
 
+// Pairs: the two blocks of mates go to the device one behind the other under one offset array of 2n + 1 entries -- D[0..n] mates
+// 1, D[n..2n] mates 2 (D[n] ends the first block and starts the second) -- and launch_pack_pairs writes the records of the joined
+// reads mate1 'N' mate2.  Everything the host keeps (lengths, record offsets) is that of the joined read.
+int lmat_reads_upload_pairs(lmat_ctx* c, const uint8_t* bases1, const uint64_t* off1, const uint8_t* bases2, const uint64_t* off2,
+                            uint64_t n, lmat_reads** out) {
+    if (!c || !out || (n && (!bases1 || !off1 || !bases2 || !off2))) return LMAT_E_ARG;
+    hipSetDevice(c->device);
+    std::vector<uint64_t> rec_off(n + 1, 0), d(2 * n + 1, 0);
+    uint32_t max_len = 0, min_len = 0xFFFFFFFFu;
+    std::vector<uint32_t> lens(n);
+    const uint64_t sum1 = n ? off1[n] - off1[0] : 0, sum2 = n ? off2[n] - off2[0] : 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t l1 = off1[i + 1] - off1[i], l2 = off2[i + 1] - off2[i];
+        if (off1[i + 1] < off1[i] || off2[i + 1] < off2[i]) return set_err(c, LMAT_E_ARG, "offsets must ascend");
+        if (l1 > 0x7FFFFFFF || l2 > 0x7FFFFFFF || l1 + 1 + l2 > 0x7FFFFFFF) return set_err(c, LMAT_E_ARG, "read too long");
+        const uint32_t len = (uint32_t)(l1 + 1 + l2);
+        max_len = std::max(max_len, len);
+        min_len = std::min(min_len, len);
+        lens[i] = len;
+        rec_off[i + 1] = rec_off[i] + rec_words(len);
+        d[i + 1] = off1[i + 1] - off1[0];
+        d[n + i + 1] = sum1 + (off2[i + 1] - off2[0]);
+    }
+    int rc = reads_alloc(c, rec_off, max_len, min_len, out);
+    if (rc) return rc;
+    (*out)->lens = lens;
+    if (!n) return LMAT_OK;
+    uint8_t* d_b = nullptr;
+    uint64_t* d_o = nullptr;
+    // one step fails: nothing is left behind, and the caller gets no handle with its error
+    auto step = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return true;
+        hipStreamSynchronize(c->stream);   // (copies already queued read `d` and write the buffers freed below)
+        if (d_b) hipFree(d_b);
+        if (d_o) hipFree(d_o);
+        lmat_reads_free(c, *out);
+        *out = nullptr;
+        set_err(c, LMAT_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+        return false;
+    };
+    if (!step(hipMalloc((void**)&d_b, sum1 + sum2 + 32), "hipMalloc (mates)")) return LMAT_E_DEVICE;  // (whole dwords are read: the one holding a block's last base may end past it)
+    if (!step(hipMalloc((void**)&d_o, (2 * n + 1) * 8), "hipMalloc (offsets)")) return LMAT_E_DEVICE;
+    if (sum1 && !step(hipMemcpyAsync(d_b, bases1 + off1[0], sum1, hipMemcpyHostToDevice, c->stream), "copy of mates 1")) return LMAT_E_DEVICE;
+    if (sum2 && !step(hipMemcpyAsync(d_b + sum1, bases2 + off2[0], sum2, hipMemcpyHostToDevice, c->stream), "copy of mates 2")) return LMAT_E_DEVICE;
+    if (!step(hipMemcpyAsync(d_o, d.data(), (2 * n + 1) * 8, hipMemcpyHostToDevice, c->stream), "copy of the offsets")) return LMAT_E_DEVICE;
+    launch_pack_pairs(d_b, d_o, d_o + n, 1, (*out)->rec_off, (*out)->words, n, c->stream);
+    if (!step(hipStreamSynchronize(c->stream), "pack_pairs_kernel")) return LMAT_E_DEVICE;
+    hipFree(d_b); hipFree(d_o);
+    return LMAT_OK;
+}
+
 int lmat_reads_synth(lmat_ctx* c, uint64_t n, const uint32_t* lengths, uint32_t n_lengths, uint64_t seed, lmat_reads** out) {
     if (!c || !out || !lengths || !n_lengths) return LMAT_E_ARG;
     if (!c->db_ready || !c->synth_genome_len) return set_err(c, LMAT_E_ARG, "synthetic reads need lmat_synth_db_build");
@@ -2211,6 +2262,10 @@ int lmat_stream_create(lmat_ctx* c, uint64_t max_reads, uint64_t max_bases, uint
     bool ok = hipStreamCreateWithFlags(&st->s_h2d, hipStreamNonBlocking) == hipSuccess &&
               hipMalloc(&st->d_scratch_counts, c->counts_bytes) == hipSuccess;
     const uint64_t max_words = max_bases / 16 + max_bases / 32 + 3 * max_reads + 16;  // rec_words summed, rounded up per read
+    // A paired batch (stream_submit<PAIRS>) of n pairs counts 2n reads and B = sum(l1 + l2) + n bases -- B is the sum of the JOINED
+    // lengths -- against these limits.  Its n records take sum(1 + ceil(len / 16) + ceil(len / 32)) <= 3n + B / 16 + B / 32 words,
+    // within max_words as 2n <= max_reads and B <= max_bases; its 2n + 1 offsets fit d_off and h_off (max_reads + 1 entries), its
+    // mates' sum(l1 + l2) = B - n bytes fit d_bases, and its n reads fit the class lists, rec_off and the results (max_reads each).
     for (auto& sl : st->slots) {
         if (!ok) break;
         sl.cand_cap = cands_per_read ? (uint64_t)cands_per_read * max_reads + (uint64_t)kCandSubs * 2048 : 0;  // (+ what the sub-cursors may leave unused: kernels.hpp)
@@ -2281,8 +2336,16 @@ static int stream_launch(lmat_stream* st, lmat_stream::Slot& sl, bool to_scratch
 }
 
 // queues the acquired slot; ext_bases != nullptr: the reads are ext_off[0..n] (any base offset) inside the caller's own
-// pinned buffer ext_bases instead of the slot's input buffers
-static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_t* ext_bases, const uint64_t* ext_off) {
+// pinned buffer ext_bases instead of the slot's input buffers.
+// PAIRS: n pairs, each joined on the device into one read  mate1 'N' mate2  of l1 + 1 + l2 bases -- all the
+// bookkeeping below is that of the joined reads.  PAIRS == 1: the slot holds the 2n mates in turn under h_off[0..2n] (mate 2's
+// offsets are mate 1's moved on by one entry, a pair advances by two).  PAIRS == 2: two caller-owned blocks, copied into the
+// slot's device buffer one behind the other under h_off[0..n] (mates 1) and h_off[n..2n] (mates 2, moved behind the first block:
+// entry n ends the one and starts the other).  Either way 2n + 1 offsets, which is why a batch counts 2n reads.
+extern "C++" {  // (a template: not among the C-linkage definitions around it)
+template <int PAIRS>
+static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_t* ext_bases, const uint64_t* ext_off,
+                         const uint8_t* ext_bases2 = nullptr, const uint64_t* ext_off2 = nullptr) {
     if (!st) return LMAT_E_ARG;
     static const bool dbg = getenv("LMAT_DEBUG_STREAM") != nullptr;
     const auto T0 = std::chrono::steady_clock::now();
@@ -2290,20 +2353,38 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
     lmat_ctx* c = st->c;
     lmat_stream::Slot& sl = st->slots[st->head % st->slots.size()];
     if (sl.state != 1) return set_err(c, LMAT_E_ARG, "lmat_stream_acquire first");
-    if (ext_bases) {
+    constexpr uint64_t S = PAIRS == 1 ? 2 : 1;   // offset entries from one read (pair) to the next
+    const uint64_t O2 = PAIRS == 1 ? 1 : n;      // PAIRS: mate 2's offsets are h_off + O2
+    const uint64_t n_off = PAIRS ? 2 * n : n;    // h_off[0..n_off]
+    uint64_t sum1 = 0;                           // PAIRS == 2: bytes of the first block
+    bool from0 = true;                           // PAIRS == 2: the caller's offsets start at 0 (decides the statistic only, below)
+    if (PAIRS && n > st->max_reads / 2) { sl.state = 0; return set_err(c, LMAT_E_ARG, "batch larger than the stream was created for"); }
+    if (PAIRS == 2) {
+        const uint64_t base1 = n ? ext_off[0] : 0, base2 = n ? ext_off2[0] : 0;
+        sum1 = n ? ext_off[n] - base1 : 0;
+        from0 = base1 == 0 && base2 == 0;
+        sl.h_off[0] = 0;   // (n == 0: the caller's offset pointers may be null)
+        for (uint64_t i = 1; i <= n; ++i) sl.h_off[i] = ext_off[i] - base1;
+        for (uint64_t i = 1; i <= n; ++i) sl.h_off[n + i] = sum1 + (ext_off2[i] - base2);
+        ext_bases += base1;
+        ext_bases2 += base2;
+    } else if (ext_bases) {
         if (n > st->max_reads) { sl.state = 0; return set_err(c, LMAT_E_ARG, "batch larger than the stream was created for"); }
         const uint64_t base = n ? ext_off[0] : 0;
-        for (uint64_t i = 0; i <= n; ++i) sl.h_off[i] = ext_off[i] - base;
+        sl.h_off[0] = 0;   // (n == 0: ext_off may be null)
+        for (uint64_t i = 1; i <= n; ++i) sl.h_off[i] = ext_off[i] - base;
         ext_bases += base;
     }
-    if (n > st->max_reads || (n && sl.h_off[n] > st->max_bases)) { sl.state = 0; return set_err(c, LMAT_E_ARG, "batch larger than the stream was created for"); }
+    // (PAIRS: the joined reads hold one base more per pair than the mates)
+    if (n > st->max_reads || (n && (sl.h_off[n_off] > st->max_bases || (PAIRS && sl.h_off[n_off] + n > st->max_bases)))) { sl.state = 0; return set_err(c, LMAT_E_ARG, "batch larger than the stream was created for"); }
     if (sl.cand_cap && (!sl.d_cands || !sl.h_cands)) { sl.state = 0; return set_err(c, LMAT_E_NOMEM, "this slot lost its candidate buffer when it could not grow"); }
     hipSetDevice(c->device);
     // record offsets and the length classes of the fast kernels: two passes over the n offsets, split over a few host
     // threads when the batch is large (2 M reads took 12 ms in one thread, longer than the GPU needs for them)
     const uint32_t k = (uint32_t)c->dev.k;
     const int nt = n >= (1u << 18) ? 4 : 1;
-    struct Part { uint64_t words = 0, cn[kNCls] = {0, 0, 0, 0}; uint32_t max_len = 0, min_len = 0xFFFFFFFFu; bool bad = false; };
+    struct Part { uint64_t words = 0, cn[kNCls] = {0, 0, 0, 0}; uint32_t max_len = 0, min_len = 0xFFFFFFFFu; bool bad = false;
+                  uint32_t max1 = 0, min1 = 0xFFFFFFFFu, max2 = 0, min2 = 0xFFFFFFFFu; };   // (PAIRS: the mates' own lengths)
     std::vector<Part> part(nt);
     auto span = [&](int t, uint64_t& lo, uint64_t& hi) { lo = n * (uint64_t)t / nt; hi = n * (uint64_t)(t + 1) / nt; };
     auto pass1 = [&](int t) {
@@ -2311,8 +2392,19 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         span(t, lo, hi);
         Part& p = part[t];
         for (uint64_t i = lo; i < hi; ++i) {
-            const uint64_t len = sl.h_off[i + 1] - sl.h_off[i];
-            if (sl.h_off[i + 1] < sl.h_off[i] || len > 0x7FFFFFFF) { p.bad = true; return; }
+            uint64_t len;
+            if (PAIRS) {
+                const uint64_t a0 = sl.h_off[i * S], a1 = sl.h_off[i * S + 1], b0 = sl.h_off[O2 + i * S], b1 = sl.h_off[O2 + i * S + 1];
+                if (a1 < a0 || b1 < b0 || a1 - a0 > 0x7FFFFFFF || b1 - b0 > 0x7FFFFFFF) { p.bad = true; return; }
+                const uint32_t l1 = (uint32_t)(a1 - a0), l2 = (uint32_t)(b1 - b0);
+                p.max1 = std::max(p.max1, l1); p.min1 = std::min(p.min1, l1);
+                p.max2 = std::max(p.max2, l2); p.min2 = std::min(p.min2, l2);
+                len = (uint64_t)l1 + 1 + l2;
+                if (len > 0x7FFFFFFF) { p.bad = true; return; }
+            } else {
+                len = sl.h_off[i + 1] - sl.h_off[i];
+                if (sl.h_off[i + 1] < sl.h_off[i] || len > 0x7FFFFFFF) { p.bad = true; return; }
+            }
             p.max_len = std::max<uint32_t>(p.max_len, (uint32_t)len);
             p.min_len = std::min<uint32_t>(p.min_len, (uint32_t)len);
             p.words += rec_words((uint32_t)len);
@@ -2326,7 +2418,8 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         span(t, lo, hi);
         uint64_t w = wbase[t], cpos[kNCls] = {cbase[kNCls * t], cbase[kNCls * t + 1], cbase[kNCls * t + 2], cbase[kNCls * t + 3]};
         for (uint64_t i = lo; i < hi; ++i) {
-            const uint32_t len = (uint32_t)(sl.h_off[i + 1] - sl.h_off[i]);
+            const uint32_t len = PAIRS ? (uint32_t)((sl.h_off[i * S + 1] - sl.h_off[i * S]) + 1 + (sl.h_off[O2 + i * S + 1] - sl.h_off[O2 + i * S]))
+                                       : (uint32_t)(sl.h_off[i + 1] - sl.h_off[i]);
             sl.h_rec_off[i] = w;
             w += rec_words(len);
             const uint32_t P = len >= k ? len - k + 1 : 0;
@@ -2342,19 +2435,26 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         for (auto& x : th) x.join();
     };
     run_parts(pass1);
-    uint32_t max_len = 0, min_len = 0xFFFFFFFFu;
+    uint32_t max_len = 0, min_len = 0xFFFFFFFFu, max1 = 0, min1 = 0xFFFFFFFFu, max2 = 0, min2 = 0xFFFFFFFFu;
     uint64_t cn[kNCls] = {0, 0, 0, 0};
     for (int t = 0; t < nt; ++t) {
         if (part[t].bad) { sl.state = 0; return set_err(c, LMAT_E_ARG, "offsets must ascend"); }
         max_len = std::max(max_len, part[t].max_len);
         min_len = std::min(min_len, part[t].min_len);
+        max1 = std::max(max1, part[t].max1); min1 = std::min(min1, part[t].min1);
+        max2 = std::max(max2, part[t].max2); min2 = std::min(min2, part[t].min2);
         wbase[t + 1] = wbase[t] + part[t].words;
         for (int j = 0; j < kNCls; ++j) { cbase[kNCls * (t + 1) + j] = cbase[kNCls * t + j] + part[t].cn[j]; cn[j] += part[t].cn[j]; }
     }
     // reads of one length (an untrimmed sequencer run): offsets and record offsets are i * length and i * words -- made on the
     // device, nothing computed here and 16 bytes per read less to copy in
     // (the slot's own offsets may start anywhere -- the general path copies them as given --, i * length holds from 0 only)
-    const bool uniform = n > 0 && min_len == max_len && sl.h_off[0] == 0;
+    // (pairs: every mate 1 of one length and every mate 2 of one -- an untrimmed 2 x 150 run -- laid out from 0.  For two caller-owned
+    // blocks "from 0" is not needed for correctness -- their offsets are rebased into the slot and the copies start at the first
+    // mate, so device-made offsets would be right from any start --: it is the stated condition of the `uniform` statistic, and such a
+    // batch runs the general path, which is right as well)
+    const bool uniform = PAIRS ? n > 0 && min1 == max1 && min2 == max2 && sl.h_off[0] == 0 && from0
+                               : n > 0 && min_len == max_len && sl.h_off[0] == 0;
     if (!uniform) run_parts(pass2);
     sl.h_rec_off[n] = wbase[nt];
     lap("offsets done");
@@ -2371,9 +2471,12 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         return err_read_too_long(c);
     }
     if (n) {
-        HIPCHK(c, hipMemcpyAsync(sl.d_bases, ext_bases ? ext_bases : sl.h_bases, sl.h_off[n], hipMemcpyHostToDevice, st->s_h2d));
+        if (PAIRS == 2) {
+            if (sum1) HIPCHK(c, hipMemcpyAsync(sl.d_bases, ext_bases, sum1, hipMemcpyHostToDevice, st->s_h2d));
+            if (sl.h_off[n_off] > sum1) HIPCHK(c, hipMemcpyAsync(sl.d_bases + sum1, ext_bases2, sl.h_off[n_off] - sum1, hipMemcpyHostToDevice, st->s_h2d));
+        } else HIPCHK(c, hipMemcpyAsync(sl.d_bases, ext_bases ? ext_bases : sl.h_bases, sl.h_off[n_off], hipMemcpyHostToDevice, st->s_h2d));
         if (!uniform) {
-            HIPCHK(c, hipMemcpyAsync(sl.d_off, sl.h_off, (n + 1) * 8, hipMemcpyHostToDevice, st->s_h2d));
+            HIPCHK(c, hipMemcpyAsync(sl.d_off, sl.h_off, (n_off + 1) * 8, hipMemcpyHostToDevice, st->s_h2d));
             HIPCHK(c, hipMemcpyAsync(sl.reads.rec_off, sl.h_rec_off, (n + 1) * 8, hipMemcpyHostToDevice, st->s_h2d));
         }
         if (used > 1)
@@ -2385,8 +2488,13 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         ++(uniform ? st->n_uniform : st->n_general);
         st->n_threaded += nt > 1;
         st->n_cls_sent += used > 1;
-        if (uniform) launch_fill_offsets(sl.d_off, sl.reads.rec_off, n, max_len, c->stream);
-        launch_pack_reads(sl.d_bases, sl.d_off, sl.reads.rec_off, sl.reads.words, n, c->stream);
+        if (PAIRS) {
+            if (uniform) launch_fill_pair_offsets(sl.d_off, sl.reads.rec_off, n, max1, max2, PAIRS == 2, c->stream);
+            launch_pack_pairs(sl.d_bases, sl.d_off, sl.d_off + O2, (uint32_t)S, sl.reads.rec_off, sl.reads.words, n, c->stream);
+        } else {
+            if (uniform) launch_fill_offsets(sl.d_off, sl.reads.rec_off, n, max_len, c->stream);
+            launch_pack_reads(sl.d_bases, sl.d_off, sl.reads.rec_off, sl.reads.words, n, c->stream);
+        }
         const int rc = stream_launch(st, sl, false);
         if (rc) {  // (an allocation failed: the copies and the pack kernel are already queued on this slot's buffers -- let them drain before the slot is handed out again)
             hipEventSynchronize(sl.ev_up);
@@ -2401,10 +2509,17 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
     ++st->head;
     return LMAT_OK;
 }
-int lmat_stream_submit(lmat_stream* st, uint64_t n, uint64_t tag) { return stream_submit(st, n, tag, nullptr, nullptr); }
+}  // extern "C++"
+int lmat_stream_submit(lmat_stream* st, uint64_t n, uint64_t tag) { return stream_submit<0>(st, n, tag, nullptr, nullptr); }
 int lmat_stream_submit_from(lmat_stream* st, const uint8_t* bases, const uint64_t* off, uint64_t n, uint64_t tag) {
     if (!st || (n && (!bases || !off))) return LMAT_E_ARG;
-    return stream_submit(st, n, tag, bases ? bases : (const uint8_t*)"", off);
+    return stream_submit<0>(st, n, tag, bases ? bases : (const uint8_t*)"", off);
+}
+int lmat_stream_submit_pairs(lmat_stream* st, uint64_t n_pairs, uint64_t tag) { return stream_submit<1>(st, n_pairs, tag, nullptr, nullptr); }
+int lmat_stream_submit_pairs_from(lmat_stream* st, const uint8_t* bases1, const uint64_t* off1, const uint8_t* bases2, const uint64_t* off2,
+                                  uint64_t n_pairs, uint64_t tag) {
+    if (!st || (n_pairs && (!bases1 || !off1 || !bases2 || !off2))) return LMAT_E_ARG;
+    return stream_submit<2>(st, n_pairs, tag, bases1 ? bases1 : (const uint8_t*)"", off1, bases2 ? bases2 : (const uint8_t*)"", off2);
 }
 int lmat_host_alloc(uint64_t bytes, void** out) {
     if (!out) return LMAT_E_ARG;

@@ -61,6 +61,10 @@ static void usage(const char* exe) {
     std::cout << "-o <output path> [-l <human bias>] -c <tax tree file> -e <depth file> -f <32to16 map> [-w <rank map>]" << std::endl;
     std::cout << "[-x min score] [-j min kmers] [-z min found kmers] [-b sdiff] [-p] [-a] [-q] [-h:turn phiX screening off]" << std::endl;
     std::cout << "[-V:print version and exit] [-H:print this usage help and exit]" << std::endl;
+    std::cout << "[-2 <mates 2 file>] paired-end: the i-th read of -i and the i-th read of -2 are classified as one read," << std::endl;
+    std::cout << "     mate 1, an N, mate 2, under mate 1's header (what merge_fastq_reads_with_N_separator.pl writes to disk); both" << std::endl;
+    std::cout << "     files are read with the same -q setting; mate names are not compared (upstream's check compares mate 1's" << std::endl;
+    std::cout << "     name with itself); files that hold different numbers of reads are an error; not with -i -" << std::endl;
 }
 
 static bool is_list_file(const std::string& fn) {
@@ -109,8 +113,9 @@ static BasePool g_pool;
 
 struct Batch {
     uint8_t* bases = nullptr;         // pooled, pinned; nb bytes used
-    size_t nb = 0;
+    size_t nb = 0, nb2 = 0;           // (nb2, off2: the second file's mates of a paired batch, below)
     std::vector<uint64_t> off{0};
+    std::vector<uint64_t> off2;       // empty: single reads; else [n+1] into bases2()
     std::string hdr_blob;             // headers back to back
     std::vector<uint64_t> hoff{0};    // [n+1] into hdr_blob
     Batch() { bases = g_pool.get(); }
@@ -127,7 +132,22 @@ struct Batch {
         return true;
     }
     void add_hdr(const char* p, size_t len) { hdr_blob.append(p, len); hoff.push_back(hdr_blob.size()); }
-    void clear() { nb = 0; overflow = false; off.assign(1, 0); hdr_blob.clear(); hoff.assign(1, 0); }
+    void clear() { nb = 0; nb2 = 0; overflow = false; off.assign(1, 0); off2.clear(); hdr_blob.clear(); hoff.assign(1, 0); }
+    // -2 (paired-end): the mates of the second file lie in the upper half of the same pinned buffer, under offsets of their own;
+    // read i of the batch is then mate 1, an N, mate 2 (joined on the GPU; the formatter writes the same text)
+    const uint8_t* bases2() const { return bases + g_pool.cap / 2; }
+    bool paired() const { return !off2.empty(); }
+    // both mates fit their halves, and the joined reads (a base more per pair) the GPU's batch
+    bool pair_fits(size_t l1, size_t l2) const { return nb + l1 <= g_pool.cap / 2 && nb2 + l2 <= g_pool.cap - g_pool.cap / 2 && nb + nb2 + l1 + l2 + n() + 1 <= g_pool.cap; }
+    void add_pair(const std::string& m1, const std::string& m2) {
+        if (off2.empty()) off2.assign(1, 0);
+        memcpy(bases + nb, m1.data(), m1.size());
+        nb += m1.size();
+        off.push_back(nb);
+        memcpy(bases + g_pool.cap / 2 + nb2, m2.data(), m2.size());
+        nb2 += m2.size();
+        off2.push_back(nb2);
+    }
 };
 
 // CPUs this process may actually use: the cgroup quota when there is one (a container with 16 CPUs on a 256-thread host
@@ -267,11 +287,11 @@ int main(int argc, char* argv[]) {
     float min_score = 0.0f;
     int min_kmer = 35, min_fnd_kmer = 1;
     lmat_params prm = {1.0f, 3.0f, 0.0f, 35, 1, 0, 1};
-    std::string rank_map_file, rank_ids, kmer_db_fn, query_fn, ofbase, tax_tree_fn, depth_file, id_bit_conv_fn, plasmid_file, rand_hits_file;
+    std::string rank_map_file, rank_ids, kmer_db_fn, query_fn, query2_fn, ofbase, tax_tree_fn, depth_file, id_bit_conv_fn, plasmid_file, rand_hits_file;
     bool fastq = false, prn_read = true;
     int permissive = 0, max_count = 0;
     std::string rank_table_file;
-    while ((c = getopt(argc, argv, "u:ahn:j:b:ye:w:pk:c:v:k:i:d:l:t:r:sm:o:x:f:g:z:qVH")) != -1) {
+    while ((c = getopt(argc, argv, "u:ahn:j:b:ye:w:pk:c:v:k:i:d:l:t:r:sm:o:x:f:g:z:qVH2:")) != -1) {
         switch (c) {
             case 'h': prm.screen_phix = 0; break;
             case 'r': plasmid_file = optarg; break;
@@ -297,6 +317,7 @@ int main(int argc, char* argv[]) {
             case 'k': k_size = atoi(optarg); break;
             case 'g': max_count = atoi(optarg); break;
             case 'i': query_fn = optarg; break;
+            case '2': query2_fn = optarg; break;
             case 'd': kmer_db_fn = optarg; break;
             case 'o': ofbase = optarg; break;
             case 'V': std::cout << "LMAT version " << LMAT_VERSION << std::endl; exit(0);
@@ -314,6 +335,12 @@ int main(int argc, char* argv[]) {
         usage(argv[0]);
         return -1;
     }
+    if (!query2_fn.empty() && (query_fn == "-" || query2_fn == "-")) {
+        std::cerr << "ERROR! -2 (paired-end reads) needs two files: not with -i -" << std::endl;
+        usage(argv[0]);
+        return -1;
+    }
+    const bool paired = !query2_fn.empty();
     // no -f: a database of 32-bit taxids (upstream's TID_SIZE=32 build); storage codes come from the tree
     prm.min_score = min_score;
     prm.min_kmer = min_kmer;
@@ -532,7 +559,8 @@ int main(int argc, char* argv[]) {
     const char* map_base = nullptr;
     size_t map_size = 0;
     static const bool fastq_seq = getenv("LMAT_FASTQ_SEQUENTIAL") && atoi(getenv("LMAT_FASTQ_SEQUENTIAL")) != 0;  // (the one-thread reader, for A/B runs)
-    if ((!fastq || !fastq_seq) && query_fn != "-") {
+    // (-2: both files go through the one-thread reader below, a pair at a time)
+    if ((!fastq || !fastq_seq) && query_fn != "-" && !paired) {
         int fd = open(query_fn.c_str(), O_RDONLY);
         struct stat sb;
         if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {
@@ -645,6 +673,54 @@ int main(int argc, char* argv[]) {
             parsed.close();
             return;
         }
+        if (paired) {
+            // Two files, read in step by the sequential reader (all its quirks, per file): the i-th read of the one with the i-th of
+            // the other, under the first file's header.  A batch is at most kBatch / 2 pairs (a pair counts two reads in the ring).
+            std::ifstream qf2(query2_fn.c_str());
+            if (!qf2) {
+                std::lock_guard<std::mutex> l(fail_m);
+                if (!failed.exchange(true)) fail_msg = "Did not open for reading: " + query2_fn;
+                parsed.close();
+                return;
+            }
+            FastxReader rd1(*in, fastq), rd2(qf2, fastq);
+            std::string m1, m2, h1, h2;
+            bool more = true, have_pending = false;
+            uint64_t next_seq = 0;
+            auto fail_input = [&](const std::string& msg) {
+                std::lock_guard<std::mutex> l(fail_m);
+                if (!failed.exchange(true)) fail_msg = msg;
+                more = false;
+            };
+            while (more) {
+                auto tp0 = now();
+                std::unique_ptr<Work> w(new Work());
+                Batch& b = w->b;
+                while (b.n() < kBatch / 2 && b.nb + b.nb2 < kPiece) {   // (a batch of about a piece of bases, as for one file)
+                    if (!have_pending) {
+                        const bool g1 = rd1.next(m1, h1), g2 = rd2.next(m2, h2);
+                        if (g1 != g2)
+                            fail_input("input: " + (g1 ? query_fn : query2_fn) + " holds more reads than " + (g1 ? query2_fn : query_fn) + " (" + std::to_string(read_count) +
+                                       " pairs read): paired-end files must hold the same number of reads");
+                        if (!g1 || !g2) { more = false; break; }
+                    }
+                    have_pending = false;
+                    if (!b.pair_fits(m1.size(), m2.size())) {
+                        if (b.n() == 0) fail_input("input: a pair of " + std::to_string(m1.size()) + " + " + std::to_string(m2.size()) + " bases exceeds the batch buffer");
+                        else have_pending = true;  // goes into the next batch
+                        break;
+                    }
+                    ++read_count;
+                    b.add_hdr(h1.data(), h1.size());
+                    b.add_pair(m1, m2);
+                }
+                if (!more) std::cout << "Total reads loaded: " << read_count << std::endl;
+                t_parse += secs(tp0, now());
+                if (b.n() && !failed) { w->seq = next_seq++; parsed.push(std::move(w)); }
+            }
+            parsed.close();
+            return;
+        }
         FastxReader rd(*in, fastq);
         std::string read, hdr;
         bool more = true;
@@ -696,8 +772,10 @@ int main(int argc, char* argv[]) {
             for (size_t i = lo; i < hi; ++i) {
                 s.append(b.hdr_blob.data() + b.hoff[i], b.hoff[i + 1] - b.hoff[i]);
                 s += '\t';
-                if (prn_read) s.append((const char*)b.bases + b.off[i], b.off[i + 1] - b.off[i]);
-                else s += 'X';
+                if (prn_read) {
+                    s.append((const char*)b.bases + b.off[i], b.off[i + 1] - b.off[i]);
+                    if (b.paired()) { s += 'N'; s.append((const char*)b.bases2() + b.off2[i], b.off2[i + 1] - b.off2[i]); }
+                } else s += 'X';
                 s += '\t';
                 format_call(s, prm, k_size, w.res[i], cands);
             }
@@ -831,7 +909,11 @@ int main(int argc, char* argv[]) {
                     if (n == 0) { classified.push(std::move(w)); continue; }  // an empty piece keeps its place in the order
                     uint8_t* hb = nullptr;
                     uint64_t* ho = nullptr;
-                    if (n <= kBatch) {
+                    if (w->b.paired()) {  // (the reader keeps a batch of pairs within the ring's limits)
+                        if (lmat_stream_acquire(st, &hb, &ho) != LMAT_OK ||
+                            lmat_stream_submit_pairs_from(st, w->b.bases, w->b.off.data(), w->b.bases2(), w->b.off2.data(), n, w->seq) != LMAT_OK) { bail("classify"); break; }
+                        flying.push(std::move(w));
+                    } else if (n <= kBatch) {
                         if (lmat_stream_acquire(st, &hb, &ho) != LMAT_OK || lmat_stream_submit_from(st, w->b.bases, w->b.off.data(), n, w->seq) != LMAT_OK) { bail("classify"); break; }
                         flying.push(std::move(w));
                     } else {  // a piece of very short reads: more reads than a slot takes, in sub-batches one after the other
