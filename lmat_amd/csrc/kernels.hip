@@ -22,6 +22,12 @@
 #ifndef LMAT_CLOSURE_FAST
 #define LMAT_CLOSURE_FAST 1   // (A/B builds: -DLMAT_CLOSURE_FAST=0)
 #endif
+#ifndef LMAT_LIST_INLINE
+#define LMAT_LIST_INLINE 1    // (A/B builds: -DLMAT_LIST_INLINE=0: lists of three kept ids wait for K3b stage 2, two scans in stage 1)
+#endif
+#ifndef LMAT_EVEN_K
+#define LMAT_EVEN_K 3         // (A/B builds: bit 0 off: the plain variants compare digests inside a run; bit 1 off: they carry the palindrome bit)
+#endif
 #ifndef LMAT_LDS_SHIFT
 #define LMAT_LDS_SHIFT 0   // (-DLMAT_LDS_SHIFT=1: the lane shifts of the minimizer window and the repeat filter through LDS instead of DPP.
                            //  Measured in round 4, same box: 24.57 against 24.29 ms per 8 M reads -- 60 vector instructions fewer per read,
@@ -1320,6 +1326,13 @@ __device__ uint32_t g_tie_why[32];
 #else
 #define TIE_WHY(i) ((void)0)
 #endif
+#if LMAT_ABLATE
+// ablation builds: the list lengths K3b stage 1 meets in the classes that stage their list records, counted across launches -- [0] reads
+// that reach the stage (and are not handed on), [1] of them with a list of more than two kept ids (the parent's stage 2), [2] / [3] / [4]
+// with one left were lists of up to 3 / 4 / 6 ids inside the staged window completed in stage 1, [8 .. 14] distinct lists by kept
+// count: 1, 2, 3, 4, 5..6, 7..14, above 14, [15] empty lists (scripts/list_share.py reads them through lmat_ablate_list_share)
+__device__ uint32_t g_list_share[16];
+#endif
 // Tied ids at the top, decided in closed form: what k4_wave_path turns away for "another id with a count >= c0".
 // Of the closure the number of kept slots is asked, as there (chain = kept << 8 | 1 << 17 | 1 << 18).  c0 = the largest kept count,
 // TOP = the kept slots at c0: two or more, all of one depth.  By the Euler intervals, wherever the slots sit: COMMON = the proper
@@ -2248,6 +2261,9 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     static_assert(!PLAIN || (U == 160 && CPT && !INK4 && !PERM && !WIDE && !LMAT_ABLATE), "PLAIN is a variant of the headline class");
     static_assert(!UNI || PLAIN, "UNI is a variant of PLAIN");
     const int k = PLAIN ? 20 : tb.k;
+    // what k = 20 and m = 17 rule out in the front end: a k-mer twice in one run of the repeat filter (even k), a palindromic m-mer (odd m)
+    constexpr bool EVENK = PLAIN && (LMAT_EVEN_K & 1), ODDM = PLAIN && (LMAT_EVEN_K & 2);
+    static_assert(!PLAIN || (20 % 2 == 0 && 17 % 2 == 1), "EVENK: k is even; ODDM: m is odd");
     const GAS uint64_t* g_slots = (const GAS uint64_t*)tb.slots;
     const GAS uint16_t* g_arena = (const GAS uint16_t*)tb.arena;
     const GAS uint32_t* g_tid32 = (const GAS uint32_t*)tb.tid32;
@@ -2401,7 +2417,11 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         if (!CPT) { if (ok) h = lds_min_insert(hv, L::H - 1, km, p); }
         else if (CACHE) {
             const uint64_t x = f >> (2 * (kCptW - 1)), xr = rv & ((1ull << (2 * cm)) - 1);  // the m-mer at p and its reverse complement
-            u_out = (cpt_scramble(x < xr ? x : xr, cm) << 4) | (xr < x ? 2u : 0u) | (x == xr ? 1u : 0u);
+            // PLAIN: m = 17 is odd, and an m-mer equal to its own reverse complement would have a middle base equal to its own
+            // complement -- the palindrome bit is never set, so it is not computed (bit 0 stays clear; the order of the words, ties
+            // included, is what it was)
+            if constexpr (ODDM) u_out = (cpt_scramble(x < xr ? x : xr, cm) << 4) | (xr < x ? 2u : 0u);
+            else u_out = (cpt_scramble(x < xr ? x : xr, cm) << 4) | (xr < x ? 2u : 0u) | (x == xr ? 1u : 0u);
             fc_out = __ballot(fc);
         }
         // bases covered by at least one valid k-mer (read_label.cpp:987-1008): base b is covered
@@ -2459,7 +2479,8 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         const uint64_t m01 = a0 < a1 ? a0 : a1, m23 = a2 < a3 ? a2 : a3;
         const uint64_t best = m01 < m23 ? m01 : m23;
         const uint32_t j = ((uint32_t)best >> 2) & 3u, fl = (uint32_t)best & 3u;
-        const uint32_t strand = fc ? fl >> 1 : (fl == 0u ? 1u : 0u);  // the m-mer in the canonical k-mer is the larger of its pair
+        // the m-mer in the canonical k-mer is the larger of its pair (PLAIN: bit 0 of fl, the palindrome bit, is clear: see pass1_chunk)
+        const uint32_t strand = ODDM ? (fl >> 1) ^ (fc ? 0u : 1u) : (fc ? fl >> 1 : (fl == 0u ? 1u : 0u));
         const uint64_t sp = cpt_mix(best >> 4, cm);
         const int lb = PLAIN ? 2 : tb.cpt.lowbits;
         const uint32_t hi = (uint32_t)(sp >> lb), low = (uint32_t)sp & ((1u << lb) - 1);
@@ -2673,6 +2694,16 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         // bucket / minimizer position / digests of the last lanes of the previous chunk.  An invalid window carries the digest and the
         // minimizer position kNone, which no valid one has (a digest by a 2^-32 chance: a false alarm costs the exact pass below, never
         // a miss): "lane - d is valid" is then part of the compare, not three shifted copies of the valid mask on the scalar side
+        // PLAIN (k = 20): no digests.  For EVEN k a k-mer never recurs inside a run.  Take p < p' with equal canonical k-mers.  Which
+        // m-mer is the minimizer (j, counted in the canonical k-mer's direction, ties included) is a function of the canonical k-mer;
+        // in the read's direction it starts at offset j when the forward strand is the canonical one and at 3 - j otherwise (treg >>
+        // 30).  Same strand at p and p': equal offsets, so the minimizer positions p + off and p' + off differ -- two runs.  Opposite
+        // strands: the positions are equal only if p' - p = +-(2 j - 3), an odd d of 1 or 3; the k-mer at p' is the reverse
+        // complement of the one at p, S[p + d + i] = comp(S[p + k - 1 - i]) for all i, and at i = (k - 1 - d) / 2 -- an integer for
+        // even k and odd d -- a base would be its own complement.  (A k-mer equal to its own reverse complement counts as reverse at
+        // both places: the first case.)  So equal k-mers lie in two runs, which share a bucket: the two bucket filters see them, as
+        // they see every other pair.  For odd k such pairs exist (tests/test_k20_same_run_repeats.py): the generic kernel compares.
+        constexpr bool DIG = !EVENK;
         constexpr uint32_t kNone = 0xFFFFFFFFu;
         uint32_t pb = 0, pq = kNone, ps1 = kNone, ps2 = kNone, ps3 = kNone;
         uint64_t seen = 0;
@@ -2684,12 +2715,12 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         if constexpr (LSH) {
             static_assert(10 * (64 * CH + 4) <= WL<U, T, E, INK4, CPT>::XL_BLOOM, "the parked values end below the repeat filter's bits");
             WSYNC();  // (the m-mer values above are through)
-            if (lane < 3) { barr[lane] = 0u; sarr[lane] = kNone; qarr[lane] = 0xFFFF; }
+            if (lane < 3) { barr[lane] = 0u; if (DIG) sarr[lane] = kNone; qarr[lane] = 0xFFFF; }
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 if (!UNI && (uint32_t)c * 64 >= P) break;
                 barr[3 + c * 64 + lane] = hreg[c];
-                sarr[3 + c * 64 + lane] = lane_bit(okm[c]) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
+                if (DIG) sarr[3 + c * 64 + lane] = lane_bit(okm[c]) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
                 qarr[3 + c * 64 + lane] = lane_bit(okm[c]) ? (uint16_t)((uint32_t)c * 64 + lane + (treg[c] >> 30)) : (uint16_t)0xFFFF;
             }
             WSYNC();
@@ -2699,23 +2730,26 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             if (!UNI && (uint32_t)c * 64 >= P) break;
             const uint64_t V = okm[c];
             const uint32_t b = hreg[c];
-            const uint32_t sig = lane_bit(V) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
+            const uint32_t sig = DIG && lane_bit(V) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
             const uint32_t q = lane_bit(V) ? (uint32_t)c * 64 + lane + (treg[c] >> 30) : (LSH ? 0xFFFFu : kNone);  // where the k-mer's minimizer starts in the read
-            uint32_t bprev, qprev, s1, s2, s3;
+            uint32_t bprev, qprev, s1 = 0, s2 = 0, s3 = 0;
             if constexpr (LSH) {
                 bprev = barr[c * 64 + lane + 2];
                 qprev = qarr[c * 64 + lane + 2];
-                s1 = sarr[c * 64 + lane + 2]; s2 = sarr[c * 64 + lane + 1]; s3 = sarr[c * 64 + lane];
+                if constexpr (DIG) { s1 = sarr[c * 64 + lane + 2]; s2 = sarr[c * 64 + lane + 1]; s3 = sarr[c * 64 + lane]; }
             } else {
                 bprev = (uint32_t)__builtin_amdgcn_update_dpp((int)pb, (int)b, 0x138, 0xf, 0xf, false);  // wave_shr:1
                 qprev = (uint32_t)__builtin_amdgcn_update_dpp((int)pq, (int)q, 0x138, 0xf, 0xf, false);
-                s1 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps1, (int)sig, 0x138, 0xf, 0xf, false);
-                s2 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps2, (int)s1, 0x138, 0xf, 0xf, false);
-                s3 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps3, (int)s2, 0x138, 0xf, 0xf, false);
+                if constexpr (DIG) {
+                    s1 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps1, (int)sig, 0x138, 0xf, 0xf, false);
+                    s2 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps2, (int)s1, 0x138, 0xf, 0xf, false);
+                    s3 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps3, (int)s2, 0x138, 0xf, 0xf, false);
+                }
             }
             // lane masks, combined on the scalar side: a ballot of `a && b` goes through a 0/1 register and a compare, a ballot of
             // one compare is the compare
-            uint64_t hitm = V & (__ballot(sig == s1) | __ballot(sig == s2) | __ballot(sig == s3));
+            uint64_t hitm = 0;
+            if constexpr (DIG) hitm = V & (__ballot(sig == s1) | __ballot(sig == s2) | __ballot(sig == s3));
             const uint64_t openm = V & ~(__ballot(b == bprev) & __ballot(q == qprev));  // lanes that open a group
             uint32_t both = 0;
             if (lane_bit(openm)) {
@@ -2729,9 +2763,11 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             if constexpr (!LSH) {
                 pb = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
                 pq = (uint32_t)__builtin_amdgcn_readlane((int)q, 63);
-                ps1 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 63);
-                ps2 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 62);
-                ps3 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 61);
+                if constexpr (DIG) {
+                    ps1 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 63);
+                    ps2 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 62);
+                    ps3 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 61);
+                }
             }
         }
         suspect = seen != 0;
@@ -3158,6 +3194,12 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     // what lies beyond -- lists 41.. of a read, ids 15.. of a list -- takes the loads from memory as before.
     constexpr bool LSTAGE = CPT && !INK4 && !WIDE && U <= 512;
     constexpr uint32_t kStageLists = 40;
+    // INL: a staged list of kInlineIds = 3 kept ids is completed in stage 1 as well -- both id orders are words 3 .. 8 of its record,
+    // one 16-bit word past the 16 bytes stage 1 reads anyway.  Three, not more: on the bench workload 96 % of the reads that get
+    // here have a list of more than two ids, 89 % of those have none of more than three inside the window, and a bound of 4 or 6
+    // takes no further read out (profiles/list_inline_share.txt); every further id is two predicated stores on every read.
+    constexpr bool INL = LSTAGE && LMAT_LIST_INLINE;
+    constexpr uint32_t kInlineIds = 3;
     static_assert(!LSTAGE || (L::OFF_XL == L::OFF_R1 && L::OFF_R2 - L::OFF_R1 >= (int)kStageLists * 64), "the window lies under the taxid tables");
     if constexpr (LSTAGE) {
         const uint32_t nst = ndist < kStageLists ? ndist : kStageLists;
@@ -3176,10 +3218,14 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         __builtin_amdgcn_s_waitcnt(0);
     }
     WSYNC();
+#if LMAT_ABLATE
+    bool ls_today = false, ls_long[3] = {false, false, false};
+    uint32_t ls_hist[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+#endif
     for (uint32_t d0 = 0; d0 < ndist; d0 += 64) {
         const uint32_t d = d0 + lane;
         uint32_t n = 0, fl = 0, m = 0, pay = 0;
-        uint32_t w3 = 0, w4 = 0, w5 = 0, w6 = 0;
+        uint32_t w3 = 0, w4 = 0, w5 = 0, w6 = 0, w7 = 0, w8 = 0;
         if (d < ndist) {
             pay = dpay[d];
             m = dmult[d];
@@ -3187,15 +3233,65 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             w3 = w4 = pay;
             if (pay >= kListBase) {
                 u32x4 ch;  // [flags][n_kept][n_raw][ids...]
-                if (LSTAGE && d < kStageLists) ch = *(const LAS u32x4*)(xl + d * 64);
+                if (LSTAGE && d < kStageLists) {
+                    ch = *(const LAS u32x4*)(xl + d * 64);
+                    if (INL) w8 = *(const LAS uint16_t*)(xl + d * 64 + 16);  // word 8 of the staged record: the last ascending id of a list of three
+                }
                 else ch = *(const GAS u32x4*)(arena + LMAT_LIST_OFF(pay, tb.list_shift));
                 fl = ch.x & 0xFFFFu;
                 n = ch.x >> 16;
                 if constexpr (WIDE) {  // ids are (low, high) pairs: the first kept id and the first ascending one fit the 16 bytes
                     w3 = (ch.y >> 16) | (ch.z << 16);
                     w4 = (ch.z >> 16) | (ch.w << 16);
-                } else { w3 = ch.y >> 16; w4 = ch.z & 0xFFFFu; w5 = ch.z >> 16; w6 = ch.w & 0xFFFFu; }
+                } else { w3 = ch.y >> 16; w4 = ch.z & 0xFFFFu; w5 = ch.z >> 16; w6 = ch.w & 0xFFFFu; w7 = ch.w >> 16; }
             }
+        }
+#if LMAT_ABLATE
+        if constexpr (LSTAGE) {
+            const bool in = d < ndist, staged = d < kStageLists;
+            ls_today |= __ballot(in && n > 2u) != 0;
+            ls_long[0] |= __ballot(in && n > 2u && !(staged && n <= 3u)) != 0;
+            ls_long[1] |= __ballot(in && n > 2u && !(staged && n <= 4u)) != 0;
+            ls_long[2] |= __ballot(in && n > 2u && !(staged && n <= 6u)) != 0;
+            ls_hist[0] += popc64(__ballot(in && n == 1u)); ls_hist[1] += popc64(__ballot(in && n == 2u));
+            ls_hist[2] += popc64(__ballot(in && n == 3u)); ls_hist[3] += popc64(__ballot(in && n == 4u));
+            ls_hist[4] += popc64(__ballot(in && n >= 5u && n <= 6u)); ls_hist[5] += popc64(__ballot(in && n >= 7u && n <= 14u));
+            ls_hist[6] += popc64(__ballot(in && n > 14u)); ls_hist[7] += popc64(__ballot(in && n == 0u));
+        }
+#endif
+        if constexpr (INL) {
+            // One scan carries both sums: n (a 16-bit word of the record: 64 of them stay below 2^22) in bits 0..21, the positions with
+            // a non-empty list above them (at most the k-mer capacity).  The positions of lists with the negative-first flag are summed
+            // only when a list of the read has it.
+            static_assert(64u * 65535u < (1u << 22) && U < (1 << 10), "the two sums of stage 1 share a 32-bit scan");
+            const uint32_t incl2 = wave_scan_incl(n | ((n ? m : 0u) << 22));
+            const uint32_t incl = incl2 & 0x3FFFFFu;
+            const bool inl3 = n == kInlineIds && d < kStageLists;   // (n == 3 has a list record: pay >= kListBase)
+            if (d < ndist) {
+                const uint32_t s0 = nel + incl - n;
+                dn[d] = (uint16_t)n;
+                dfl[d] = (uint8_t)fl;
+                dstart[d] = (uint16_t)s0;
+                if (n != 0 && s0 < (uint32_t)E) el_d[s0] = (eld_t)d;
+                if (s0 + n <= (uint32_t)E) {  // ids and owners of the lists this stage completes
+                    if (n == 1) { el_t[s0] = (tid_t)w3; el_ta[s0] = (tid_t)w4; }
+                    else if (n == 2) {
+                        el_t[s0] = (tid_t)w3; el_t[s0 + 1] = (tid_t)w4;
+                        el_ta[s0] = (tid_t)w5; el_ta[s0 + 1] = (tid_t)w6;
+                        el_d[s0 + 1] = (eld_t)d;
+                    } else if (inl3) {
+                        el_t[s0] = (tid_t)w3; el_t[s0 + 1] = (tid_t)w4; el_t[s0 + 2] = (tid_t)w5;
+                        el_ta[s0] = (tid_t)w6; el_ta[s0 + 1] = (tid_t)w7; el_ta[s0 + 2] = (tid_t)w8;
+                        el_d[s0 + 1] = (eld_t)d; el_d[s0 + 2] = (eld_t)d;
+                    }
+                }
+            }
+            any_long |= (__ballot(n > 2u) & ~__ballot(inl3)) != 0;   // some list is left to stage 2
+            const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl2, 63);
+            if (__ballot((fl & kListNegFirst) != 0u)) cand -= wave_sum((fl & kListNegFirst) ? m : 0u);  // (quirk Q4, below)
+            fnd += tot >> 22;
+            nel += tot & 0x3FFFFFu;
+            continue;
         }
         // inclusive scan of n over the wave
         const uint32_t incl = wave_scan_incl(n);
@@ -3231,7 +3327,15 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         }
         return;
     }
-    {
+#if LMAT_ABLATE
+    if (LSTAGE && lane == 0) {
+        atomicAdd(&g_list_share[0], 1u);
+        if (ls_today) atomicAdd(&g_list_share[1], 1u);
+        for (int i = 0; i < 3; ++i) if (ls_long[i]) atomicAdd(&g_list_share[2 + i], 1u);
+        for (int i = 0; i < 8; ++i) if (ls_hist[i]) atomicAdd(&g_list_share[8 + i], ls_hist[i]);
+    }
+#endif
+    if (!INL || any_long) {  // (INL: stage 1 wrote the owners of the lists it completed, which are what the running maximum puts there)
         uint32_t carry = 0;
         for (uint32_t e0 = 0; e0 < nel; e0 += 64) {
             const uint32_t e = e0 + lane;
@@ -3250,7 +3354,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             const uint32_t e = e0 + lane;
             if (e < nel) {
                 const uint32_t d = el_d[e], n = dn[d];
-                if (n > (WIDE ? 1u : 2u)) {
+                if (n > (WIDE ? 1u : 2u) && !(INL && n == kInlineIds && d < kStageLists)) {
                     const size_t eoff = LMAT_LIST_OFF(dpay[d], tb.list_shift) + kListHdr;
                     const uint32_t j = e - dstart[d];
                     if constexpr (WIDE) {
@@ -4582,6 +4686,12 @@ extern "C" int lmat_ablate_path_why(uint32_t* out16, int reset) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(lmat::g_path_why), 64) != hipSuccess) return -1;
     if (reset) { const uint32_t z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lmat::g_path_why), z, 64) != hipSuccess) return -1; }
+    return 0;
+}
+extern "C" int lmat_ablate_list_share(uint32_t* out16, int reset) {   // K3b stage 1's list lengths (g_list_share; scripts/list_share.py)
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(lmat::g_list_share), 64) != hipSuccess) return -1;
+    if (reset) { const uint32_t z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lmat::g_list_share), z, 64) != hipSuccess) return -1; }
     return 0;
 }
 namespace lmat {
