@@ -497,6 +497,44 @@ int lmat_export_set_options(lmat_export* e, uint64_t device_budget_bytes, int pr
 int lmat_export_run(lmat_export* e, const char* taxhisto_fn /* NULL: keep the result in host memory */, lmat_export_stats* out);
 int lmat_export_fetch(lmat_export* e, uint64_t first, uint64_t count, uint64_t* kmers, uint64_t* list_off, uint32_t* tids, uint64_t tid_cap);
 int lmat_export_taxid_counts(lmat_export* e, uint32_t* tids, uint64_t* counts, uint64_t cap, uint64_t* n);
+
+/* ---- a taxonomic slice of the export: a filter on the device, ahead of the fetch ----
+ * A filter is a property of an lmat_export, set before lmat_export_run; a k-mer is kept iff ALL enabled tests pass.
+ *   where it looks   the list AS STORED: the ids, in the order, that the unfiltered export writes.  Label modes do not change it.
+ *   S                the nodes `taxa` of ctx's tree and all their descendants.  Taxa may repeat or nest (the intervals are merged).
+ *   depth            the number of proper ancestors in ctx's tree (root = 0), not the -e file's value; for a closed list
+ *                    min_lca_depth therefore tests the depth of the list's LCA.
+ *   unknown ids      an entry the context's taxonomy does not hold (conv[code] == 0 included) is OUTSIDE S and has DEPTH 0.
+ *   what is kept     ascending by k-mer and otherwise unchanged; the sanity word follows every 1500th KEPT record, counted across
+ *                    passes; the header count is the number kept (written first, patched after the last pass: 8 bytes at offset 4).
+ *                    lmat_export_stats keeps its layout: records / entries / singletons, lmat_export_fetch and
+ *                    lmat_export_taxid_counts describe the kept records.  The "records differ from lmat_db_size" check
+ *                    (LMAT_E_INTERNAL) applies to the records SCANNED.
+ *   stats            out6 = scanned, kept, dropped by the taxon test, dropped by depth, dropped by length, long lists (more than 8
+ *                    entries) judged by a whole wave; a record failing several tests is charged to the first in that order.
+ *                    ms_select: HIP-event time of the filter stage (0 without a filter).  Before a run: LMAT_E_STATE.
+ *   no filter        (never set, NULL, or one that enables no test) the run is the unfiltered run: launches, budget model, bytes.
+ *   memory           with a filter a pass takes 48 device bytes per scanned pair instead of 40 (keep flag and position), and the
+ *                    run 4 bytes per taxonomy node times three plus 256 KiB for the per-entry facts.
+ *   errors           a taxid the tree does not hold: LMAT_E_TAXONOMY.  mode != 0 with n_taxa == 0, mode == 0 with n_taxa != 0, a
+ *                    mode outside 0..3, taxa == NULL with n_taxa != 0: LMAT_E_ARG.  Any filter on a gene database: LMAT_E_ARG.
+ * lmat_db_from_export runs e (with its filter, into host memory) and hands the records to dst's ingest through the in-memory
+ * stream lmat_db_build_from_genomes uses, k taken from the source: dst ends up holding the slice as a finalized database.
+ * dst without a taxonomy: LMAT_E_STATE; dst == e's context, a gene source, an empty slice: LMAT_E_ARG; the text is
+ * lmat_export_error(e)'s. */
+#define LMAT_SLICE_ANY  1   /* keep a k-mer iff at least one list entry lies in S            */
+#define LMAT_SLICE_ALL  2   /* ... iff every list entry lies in S (clade-specific k-mers)    */
+#define LMAT_SLICE_NONE 3   /* ... iff no list entry lies in S (e.g. S = {9606}: host-free)  */
+typedef struct {
+    const uint32_t* taxa; uint32_t n_taxa;  /* S = these nodes of ctx's tree and all their descendants */
+    int mode;                               /* 0: no taxon test (then n_taxa must be 0)                 */
+    uint32_t min_lca_depth;                 /* 0: off.  keep iff every entry has tree depth >= this     */
+    uint32_t max_entries;                   /* 0: off.  keep iff the stored list has at most this many  */
+} lmat_export_filter;
+int lmat_export_set_filter(lmat_export* e, const lmat_export_filter* f /* NULL: clear */);
+int lmat_export_filter_stats(const lmat_export* e, uint64_t out6[6], double* ms_select);
+int lmat_db_from_export(lmat_ctx* dst, lmat_export* e, uint64_t table_bytes);
+
 /* A loaded database as one more input of a merge (beside lmat_build_add_taxhisto): src is exported into host memory at the time of
  * the call and its records take the path a parsed file takes.  k must match (LMAT_E_ARG); a gene database is LMAT_E_ARG. */
 int lmat_build_add_db(lmat_build* b, lmat_ctx* src);

@@ -68,6 +68,13 @@ class ExportStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ExportFilter(C.Structure):
+    """lmat_export_filter: the taxonomic slice of an export (Export.set_filter)."""
+    _fields_ = [("taxa", C.POINTER(C.c_uint32)), ("n_taxa", C.c_uint32), ("mode", C.c_int), ("min_lca_depth", C.c_uint32), ("max_entries", C.c_uint32)]
+
+
+SLICE_MODES = {"any": 1, "all": 2, "none": 3}    # LMAT_SLICE_*
+
 READ_RESULT_DTYPE = np.dtype([("status", "u1"), ("match_type", "u1"), ("cand_kmer_cnt", "<u2"), ("valid_kmers", "<i4"),
                               ("read_len", "<i4"), ("log_avg", "<f4"), ("stdev", "<f4"), ("call_tid", "<u4"),
                               ("call_score", "<f4"), ("cand_off", "<u4"), ("n_cand", "<u4"), ("bin_sel", "<i4")])
@@ -208,6 +215,9 @@ def load_library(path: str | None = None):
         "lmat_export_run": (i32, [vp, cp, P(ExportStats)]),
         "lmat_export_fetch": (i32, [vp, u64, u64, vp, vp, vp, u64]),
         "lmat_export_taxid_counts": (i32, [vp, vp, vp, u64, P(u64)]),
+        "lmat_export_set_filter": (i32, [vp, P(ExportFilter)]),
+        "lmat_export_filter_stats": (i32, [vp, P(u64), P(C.c_double)]),
+        "lmat_db_from_export": (i32, [vp, vp, u64]),
         "lmat_build_add_db": (i32, [vp, vp]),
         "lmat_genebuild_create": (i32, [vp, i32, P(vp)]),
         "lmat_genedb_build_from_genes": (i32, [vp, vp, u64]),
@@ -244,7 +254,7 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_cov_create", "lmat_cov_destroy", "lmat_cov_error", "lmat_cov_set_options", "lmat_cov_add_reads", "lmat_cov_run",
             "lmat_cov_summary", "lmat_cov_histogram",
             "lmat_export_create", "lmat_export_destroy", "lmat_export_error", "lmat_export_set_options", "lmat_export_run", "lmat_export_fetch",
-            "lmat_export_taxid_counts", "lmat_build_add_db", "lmat_table_unaddress",
+            "lmat_export_taxid_counts", "lmat_export_set_filter", "lmat_export_filter_stats", "lmat_db_from_export", "lmat_build_add_db", "lmat_table_unaddress",
             "lmat_genebuild_create", "lmat_genedb_build_from_genes",
             "lmat_debug_stream_stats", "lmat_debug_reads_words",
             "lmat_reads_upload_pairs", "lmat_stream_submit_pairs", "lmat_stream_submit_pairs_from"]
@@ -547,6 +557,30 @@ class Export:
     def set_options(self, budget_bytes=0, prefix_bits=-1):
         self._chk(self.lib.lmat_export_set_options(self.h, int(budget_bytes), int(prefix_bits)))
 
+    def set_filter(self, taxa=(), mode=None, min_lca_depth=0, max_entries=0):
+        """The taxonomic slice (lmat_export_set_filter): S = the subtrees of `taxa`; mode "any" | "all" | "none" keeps a k-mer iff any /
+        every / no entry of its stored list lies in S; min_lca_depth: every entry at least that deep in the tree; max_entries: lists of at
+        most that many.  All enabled tests must pass.  Everything at its default clears the filter."""
+        if mode is not None and mode not in SLICE_MODES:
+            raise LmatError(-1, "filter mode must be None, 'any', 'all' or 'none', not %r" % (mode,))
+        t = np.ascontiguousarray(np.asarray(list(taxa), dtype=np.uint32))
+        f = ExportFilter(t.ctypes.data_as(C.POINTER(C.c_uint32)) if t.size else None, int(t.size), SLICE_MODES[mode] if mode else 0, int(min_lca_depth), int(max_entries))
+        self._chk(self.lib.lmat_export_set_filter(self.h, C.byref(f)))
+
+    def clear_filter(self):
+        self._chk(self.lib.lmat_export_set_filter(self.h, None))
+
+    def filter_stats(self):
+        """-> {"scanned", "kept", "dropped_taxon", "dropped_depth", "dropped_length", "wave_lists", "ms_select"} of the last run"""
+        out = (C.c_uint64 * 6)()
+        ms = C.c_double(0)
+        self._chk(self.lib.lmat_export_filter_stats(self.h, out, C.byref(ms)))
+        return dict(zip(("scanned", "kept", "dropped_taxon", "dropped_depth", "dropped_length", "wave_lists"), (int(v) for v in out)), ms_select=ms.value)
+
+    def into(self, dst, table_bytes=0):
+        """Run with the filter and make the result the finalized database of the engine `dst` (lmat_db_from_export)."""
+        self._chk(self.lib.lmat_db_from_export(dst.ctx, self.h, int(table_bytes)))
+
     def run(self, out=None):
         st = ExportStats()
         self._chk(self.lib.lmat_export_run(self.h, out.encode() if out is not None else None, C.byref(st)))
@@ -787,25 +821,46 @@ class Engine:
             c.close()
 
     # the database back out (lmat_export_*) ----------------------------------------------
-    def export_taxhisto(self, out=None, budget_bytes=0, prefix_bits=-1):
+    def export_taxhisto(self, out=None, budget_bytes=0, prefix_bits=-1, taxa=(), mode=None, min_lca_depth=0, max_entries=0):
         """The loaded database as tax_histo records, ascending, lists in stored order.  With `out` the file build_db reads is
-        written and the statistics (dict) returned; with out=None -> (statistics, (kmers, list_off, tids))."""
+        written and the statistics (dict) returned; with out=None -> (statistics, (kmers, list_off, tids)).
+        taxa / mode / min_lca_depth / max_entries: a taxonomic slice (Export.set_filter); its counters come under "filter"."""
         x = Export(self)
         try:
             x.set_options(budget_bytes, prefix_bits)
+            sliced = bool(len(taxa) or mode or min_lca_depth or max_entries)
+            if sliced:
+                x.set_filter(taxa, mode, min_lca_depth, max_entries)
             st = x.run(out)
+            if sliced:
+                st["filter"] = x.filter_stats()
             return st if out else (st, x.fetch())
         finally:
             x.close()
 
-    def db_taxid_counts(self, budget_bytes=0, prefix_bits=-1):
-        """frequency_counter on the loaded database: -> {"counts": {taxid: lists that hold it}, "total_tid": n, "singletons": n}"""
+    def db_taxid_counts(self, budget_bytes=0, prefix_bits=-1, taxa=(), mode=None, min_lca_depth=0, max_entries=0):
+        """frequency_counter on the loaded database: -> {"counts": {taxid: lists that hold it}, "total_tid": n, "singletons": n};
+        with the filter keywords of export_taxhisto, on that slice of it."""
         x = Export(self)
         try:
             x.set_options(budget_bytes, prefix_bits)
+            if len(taxa) or mode or min_lca_depth or max_entries:
+                x.set_filter(taxa, mode, min_lca_depth, max_entries)
             st = x.run("")
             t, c = x.taxid_counts()
             return {"counts": {int(a): int(b) for a, b in zip(t, c)}, "total_tid": st["entries"], "singletons": st["singletons"]}
+        finally:
+            x.close()
+
+    def derive_db(self, src_engine, table_bytes=0, budget_bytes=0, prefix_bits=-1, **filter):
+        """This engine's database becomes a slice of the one `src_engine` holds (needs load_taxonomy first): the filter keywords of
+        export_taxhisto select it, no file in between (lmat_db_from_export).  -> the export's statistics with the counters under "filter"."""
+        x = Export(src_engine)
+        try:
+            x.set_options(budget_bytes, prefix_bits)
+            x.set_filter(**filter)
+            x.into(self, table_bytes)
+            return {"filter": x.filter_stats()}
         finally:
             x.close()
 

@@ -8,6 +8,7 @@
 //   scan_wide_kernel   the same for 8 x u64 slot buckets: the overflow table of a compact table, or the whole table in the wide layout
 //   rocPRIM radix_sort_pairs on bits [0, 2k)
 //   dup_kernel         two equal neighbours = the table holds a key twice: reported, never de-duplicated
+//   with a filter (lmat_export_set_filter): slice_kernel, exclusive scan, scatter_kernel -- the kept pairs, still ascending
 //   len_kernel, exclusive scan, write_kernel   CSR of 32-bit ids in stored order (the three decodings of lookup_kernel, kernels.hip)
 //   radix_sort_keys + run_length_encode of the pass's ids    per-taxid counts (frequency_counter), merged on the host
 // The host fetches the pass and appends it to the result or streams it to the file, so neither memory bounds the table's size.
@@ -200,6 +201,132 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void write_kernel(DeviceTables
     }
 }
 
+// ---- the taxonomic slice (lmat_export_set_filter): between dup_kernel and len_kernel, so that everything behind it
+// sees kept records only.  facts_kernel (once per run) -> slice_kernel (keep flag per record) -> exclusive scan -> scatter_kernel.
+enum { F_KEPT = 0, F_DROP_TAXON, F_DROP_DEPTH, F_DROP_LEN, F_WAVE_LISTS, F_N };
+
+constexpr u32 kInS = 0x80000000u;   // fact word of a list entry: this bit when it lies in S, its tree depth below it; 0 for an id the taxonomy does not hold
+constexpr u64 kFilterPairBytes = 8; // device bytes a filter adds per scanned pair: keep flag and position
+
+struct SliceArgs {
+    const u32* id_fact;      // [n_ids] by internal id: singleton payloads, pair entries once found
+    const u32* code_fact;    // [65536] by stored 16-bit code
+    u32 n_ids;               // nodes + 1
+    int mode;
+    u32 min_depth, max_entries;
+};
+
+// the internal id of a 32-bit taxid (tid32[1 .. n_ids) ascends), 0 when the taxonomy does not hold it
+__device__ __forceinline__ u32 find_id(const u32* tid32, u32 n_ids, u32 tid) {
+    u32 lo = 1, hi = n_ids;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tid32[mid] < tid) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n_ids && tid32[lo] == tid ? lo : 0;
+}
+
+// iv: the merged Euler intervals of S, n_iv pairs (first tick, last tick), ascending and disjoint
+__device__ __forceinline__ u32 node_fact(const u32* tin, const u32* depth, const u32* iv, u32 n_iv, u32 id) {
+    const u32 t = tin[id];
+    u32 lo = 0, hi = n_iv;
+    while (lo < hi) {   // the intervals that start at or before t
+        const u32 mid = (lo + hi) >> 1;
+        if (iv[2 * mid] <= t) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo && t <= iv[2 * lo - 1] ? kInS : 0u) | depth[id];
+}
+
+// a thread per internal id, then per 16-bit code
+__global__ __launch_bounds__(256) void facts_kernel(const u32* tid32, const u32* conv, const u32* tin, const u32* depth, const u32* iv, u32 n_iv, u32 n_ids,
+                                                    u32* id_fact, u32* code_fact) {
+    const u32 g = blockIdx.x * 256 + threadIdx.x;
+    if (g < n_ids) id_fact[g] = g ? node_fact(tin, depth, iv, n_iv, g) : 0u;
+    else if (g - n_ids < 65536u) {
+        const u32 t = conv[g - n_ids];
+        const u32 id = t ? find_id(tid32, n_ids, t) : 0u;
+        code_fact[g - n_ids] = id ? node_fact(tin, depth, iv, n_iv, id) : 0u;
+    }
+}
+
+__device__ __forceinline__ u32 entry_fact(const DeviceTables& tb, const SliceArgs& f, const ListRef& r, u32 j) {
+    if (!r.kind) return f.code_fact[r.raw[j]];
+    const u32 id = find_id(tb.tid32, f.n_ids, (u32)r.raw[2 * j] | ((u32)r.raw[2 * j + 1] << 16));
+    return id ? f.id_fact[id] : 0u;
+}
+
+// A lane per sorted record, as write_kernel: singletons and lists of up to kShortList entries are judged by their lane, the others by the
+// whole wave in turn (entries in S summed, depths minimised across the lanes).  keep[i] = 1 iff every enabled test passes; a record that
+// fails is charged to the first of taxon, depth, length.
+__global__ __launch_bounds__(64 * kWavesPerBlock) void slice_kernel(DeviceTables tb, SliceArgs f, const u32* pays, u64 n, u32* keep, u64* fc) {
+    const u32 lane = lane_id();
+    const u64 i = ((u64)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 64 + lane;
+    const bool have = i < n;
+    u32 pay = 0, len = 0, in = 0, mind = ~kInS;
+    if (have) {
+        pay = pays[i];
+        if (pay < kListBase) {
+            const u32 w = pay < f.n_ids ? f.id_fact[pay] : 0u;
+            len = 1;
+            in = w >> 31;
+            mind = w & ~kInS;
+        } else {
+            len = list_len(tb, pay);
+            if (len <= kShortList) {
+                const ListRef r = list_ref(tb, pay);
+                for (u32 j = 0; j < len; ++j) {
+                    const u32 w = entry_fact(tb, f, r, j);
+                    in += w >> 31;
+                    mind = min(mind, w & ~kInS);
+                }
+            }
+        }
+    }
+    u64 longs = __ballot(have && pay >= kListBase && len > kShortList);
+    const u32 n_long = __popcll(longs);
+    while (longs) {
+        const int src = __ffsll((long long)longs) - 1;
+        longs &= longs - 1;
+        const u32 lp = __shfl(pay, src), ln = __shfl(len, src);
+        const ListRef r = list_ref(tb, lp);
+        u32 c = 0, d = ~kInS;
+        for (u32 j = lane; j < ln; j += 64) {
+            const u32 w = entry_fact(tb, f, r, j);
+            c += w >> 31;
+            d = min(d, w & ~kInS);
+        }
+        c = wave_sum(c);
+        d = wave_reduce(d, [](u32 x, u32 y) { return x < y ? x : y; });
+        if (lane == (u32)src) { in = c; mind = d; }
+    }
+    u32 v = 0;   // 0: kept, else the test that drops it
+    if (have) {
+        const bool taxon = f.mode == LMAT_SLICE_ANY ? in != 0 : f.mode == LMAT_SLICE_ALL ? in == len : f.mode == LMAT_SLICE_NONE ? in == 0 : true;
+        if (!taxon) v = 1;
+        else if (f.min_depth && mind < f.min_depth) v = 2;
+        else if (f.max_entries && len > f.max_entries) v = 3;
+        keep[i] = v == 0;
+    }
+    const u32 kept = __popcll(__ballot(have && v == 0)), t = __popcll(__ballot(v == 1)), d = __popcll(__ballot(v == 2)), l = __popcll(__ballot(v == 3));
+    if (lane == 0) {
+        if (kept) atomicAdd(&fc[F_KEPT], (u64)kept);
+        if (t) atomicAdd(&fc[F_DROP_TAXON], (u64)t);
+        if (d) atomicAdd(&fc[F_DROP_DEPTH], (u64)d);
+        if (l) atomicAdd(&fc[F_DROP_LEN], (u64)l);
+        if (n_long) atomicAdd(&fc[F_WAVE_LISTS], (u64)n_long);
+    }
+}
+
+// the kept pairs to their place: pos is the exclusive scan of keep, so the order stays
+__global__ __launch_bounds__(256) void scatter_kernel(const u64* keys, const u32* pays, const u32* keep, const u32* pos, u64 n, u64* keys_out, u32* pays_out) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !keep[i]) return;
+    keys_out[pos[i]] = keys[i];
+    pays_out[pos[i]] = pays[i];
+}
+
 double host_ms(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -216,6 +343,16 @@ struct lmat_export {
     std::vector<u32> tids;
     std::map<u32, u64> counts;     // lists that hold the taxid
     lmat_export_stats stats;
+    // the filter (lmat_export_set_filter): `on` when a test is enabled; iv = the merged Euler intervals of S as (first, last) tick pairs
+    struct Filter {
+        bool on = false;
+        int mode = 0;
+        u32 min_depth = 0, max_entries = 0;
+        std::vector<u32> iv;
+    } filter;
+    u64 fstats[6] = {0, 0, 0, 0, 0, 0};   // scanned, kept, dropped by taxon / depth / length, long lists judged by a wave
+    double ms_select = 0;
+    DevBuf f_tin, f_depth, f_iv, id_fact, code_fact;   // the filter's device arrays: the export's own, not the context's
 };
 
 namespace {
@@ -288,8 +425,30 @@ struct ExportRun {
     int k, pb;
     u64 cap = 0, budget = 0;
     DevBuf counters, keysA, keysB, paysA, paysB, len, off, tids, tids_sorted, uniq, ucnt, n_runs, temp;
+    DevBuf keep, pos, fcount;        // with a filter only
+    u64 pair_bytes = kPairBytes;     // ... which adds kFilterPairBytes
+    SliceArgs fa;
     LapTimer timer;
-    u64 hc[X_N];
+    u64 hc[X_N], fc[F_N];
+
+    // the filter's per-entry facts, once per run
+    int facts() {
+        const lmat::HostTaxonomy& T = c->tax;
+        const lmat_export::Filter& F = e->filter;
+        const u32 n_ids = T.n + 1, n_iv = (u32)(F.iv.size() / 2);
+        std::vector<u32> depth(T.path_len.begin(), T.path_len.end());
+        XHIP(e, ensure_all({{&e->f_tin, (size_t)n_ids * 4}, {&e->f_depth, (size_t)n_ids * 4}, {&e->f_iv, F.iv.size() * 4}, {&e->id_fact, (size_t)n_ids * 4},
+                            {&e->code_fact, 65536 * 4}, {&fcount, F_N * 8}}));
+        XHIP(e, hipMemcpyAsync(e->f_tin.p, T.tin.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, st));
+        XHIP(e, hipMemcpyAsync(e->f_depth.p, depth.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, st));
+        if (n_iv) XHIP(e, hipMemcpyAsync(e->f_iv.p, F.iv.data(), F.iv.size() * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(facts_kernel, dim3((n_ids + 65536 + 255) / 256), dim3(256), 0, st, c->dev.tid32, c->dev.conv, e->f_tin.as<u32>(), e->f_depth.as<u32>(),
+                           e->f_iv.as<u32>(), n_iv, n_ids, e->id_fact.as<u32>(), e->code_fact.as<u32>());
+        XHIP(e, hipGetLastError());
+        XHIP(e, hipStreamSynchronize(st));   // depth goes out of scope
+        fa = SliceArgs{e->id_fact.as<u32>(), e->code_fact.as<u32>(), n_ids, F.mode, F.min_depth, F.max_entries};
+        return LMAT_OK;
+    }
 
     // LMAT_OK; or `finer` set: the pass does not fit under this split
     int pass(u32 p, Sink& sink, bool& finer) {
@@ -314,7 +473,8 @@ struct ExportRun {
         XHIP(e, timer.lap(ms));
         S.ms_scan += ms;
         if (hc[X_OVERFLOW]) { finer = true; return LMAT_OK; }
-        const u64 n = hc[X_CURSOR];
+        u64 n = hc[X_CURSOR];
+        e->fstats[0] += n;
         S.from_buckets += hc[X_FROM_BUCKETS];
         S.from_overflow += hc[X_FROM_WIDE];
         if (!n) return LMAT_OK;
@@ -328,7 +488,37 @@ struct ExportRun {
         XHIP(e, timer.lap(ms));
         S.ms_sort += ms;
         ms = 0;
-        hipLaunchKernelGGL(len_kernel, dim3(g256), dim3(256), 0, st, tb, paysB.as<u32>(), n, len.as<u64>(), counters.as<u64>());
+        const u64 scanned = n;
+        const u64* keys = keysB.as<u64>();
+        const u32* pays = paysB.as<u32>();
+        if (e->filter.on) {   // the kept pairs, still ascending, into the sort's free buffers; n is the number kept from here on
+            XHIP(e, hipMemsetAsync(fcount.p, 0, F_N * 8, st));
+            hipLaunchKernelGGL(slice_kernel, dim3((u32)((n + 64 * kWavesPerBlock - 1) / (64 * kWavesPerBlock))), dim3(64 * kWavesPerBlock), 0, st, tb, fa, pays, n,
+                               keep.as<u32>(), fcount.as<u64>());
+            XHIP(e, hipGetLastError());
+            XHIP(e, with_temp(temp, [&](void* t, size_t& tbytes) {
+                return rocprim::exclusive_scan(t, tbytes, keep.as<u32>(), pos.as<u32>(), 0u, (size_t)n, rocprim::plus<u32>(), st);
+            }));
+            hipLaunchKernelGGL(scatter_kernel, dim3(g256), dim3(256), 0, st, keys, pays, keep.as<u32>(), pos.as<u32>(), n, keysA.as<u64>(), paysA.as<u32>());
+            XHIP(e, hipGetLastError());
+            XHIP(e, hipMemcpyAsync(hc, counters.p, X_N * 8, hipMemcpyDeviceToHost, st));
+            XHIP(e, hipMemcpyAsync(fc, fcount.p, F_N * 8, hipMemcpyDeviceToHost, st));
+            XHIP(e, timer.lap(ms));
+            XHIP(e, hipStreamSynchronize(st));
+            e->ms_select += ms;
+            ms = 0;
+            if (hc[X_DUP])
+                return xerr(e, LMAT_E_INTERNAL, "the table holds k-mer " + kmer_text(hc[X_DUP_KMER], k) + " twice (" + std::to_string(hc[X_DUP]) + " repeated keys in pass " + std::to_string(p) + ")");
+            e->fstats[2] += fc[F_DROP_TAXON];
+            e->fstats[3] += fc[F_DROP_DEPTH];
+            e->fstats[4] += fc[F_DROP_LEN];
+            e->fstats[5] += fc[F_WAVE_LISTS];
+            n = fc[F_KEPT];
+            if (!n) return LMAT_OK;
+            keys = keysA.as<u64>();
+            pays = paysA.as<u32>();
+        }
+        hipLaunchKernelGGL(len_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, tb, pays, n, len.as<u64>(), counters.as<u64>());
         XHIP(e, hipGetLastError());
         XHIP(e, with_temp(temp, [&](void* t, size_t& tbytes) {
             return rocprim::exclusive_scan(t, tbytes, len.as<u64>(), off.as<u64>(), 0ull, (size_t)n, rocprim::plus<u64>(), st);
@@ -338,10 +528,10 @@ struct ExportRun {
         if (hc[X_DUP])
             return xerr(e, LMAT_E_INTERNAL, "the table holds k-mer " + kmer_text(hc[X_DUP_KMER], k) + " twice (" + std::to_string(hc[X_DUP]) + " repeated keys in pass " + std::to_string(p) + ")");
         const u64 entries = hc[X_ENTRIES];
-        if (entries > 0xFFFFFFF0ull || n * kPairBytes + entries * kEntryBytes > budget) { finer = true; return LMAT_OK; }
+        if (entries > 0xFFFFFFF0ull || scanned * pair_bytes + entries * kEntryBytes > budget) { finer = true; return LMAT_OK; }
         XHIP(e, hipMemcpyAsync(off.as<u64>() + n, &hc[X_ENTRIES], 8, hipMemcpyHostToDevice, st));
         XHIP(e, ensure_all({{&tids, entries * 4}, {&tids_sorted, entries * 4}, {&uniq, entries * 4}, {&ucnt, entries * 4}}));
-        hipLaunchKernelGGL(write_kernel, dim3((u32)((n + 64 * kWavesPerBlock - 1) / (64 * kWavesPerBlock))), dim3(64 * kWavesPerBlock), 0, st, tb, paysB.as<u32>(), off.as<u64>(),
+        hipLaunchKernelGGL(write_kernel, dim3((u32)((n + 64 * kWavesPerBlock - 1) / (64 * kWavesPerBlock))), dim3(64 * kWavesPerBlock), 0, st, tb, pays, off.as<u64>(),
                            n, tids.as<u32>());
         XHIP(e, hipGetLastError());
         // per-taxid counts of the pass: its ids sorted, one run per id
@@ -358,7 +548,7 @@ struct ExportRun {
         if (sink.h_kmers.size() < n) { sink.h_kmers.resize(n); sink.h_off.resize(n + 1); }
         if (sink.h_tids.size() < entries) sink.h_tids.resize(entries);
         std::vector<u32> hu(runs), hn(runs);
-        XHIP(e, hipMemcpy(sink.h_kmers.data(), keysB.p, n * 8, hipMemcpyDeviceToHost));
+        XHIP(e, hipMemcpy(sink.h_kmers.data(), keys, n * 8, hipMemcpyDeviceToHost));
         XHIP(e, hipMemcpy(sink.h_off.data(), off.p, (n + 1) * 8, hipMemcpyDeviceToHost));
         XHIP(e, hipMemcpy(sink.h_tids.data(), tids.p, entries * 4, hipMemcpyDeviceToHost));
         if (runs) {
@@ -373,6 +563,7 @@ struct ExportRun {
         S.records += n;
         S.entries += entries;
         S.singletons += hc[X_SINGLETONS];
+        e->fstats[1] += n;
         return LMAT_OK;
     }
 };
@@ -386,6 +577,9 @@ int run_export(lmat_export* e, const char* fn, int pb, bool& finer) {
     e->stats.prefix_bits = pb;
     e->kmers.clear(); e->tids.clear(); e->counts.clear();
     e->list_off.assign(1, 0);
+    memset(e->fstats, 0, sizeof(e->fstats));
+    e->ms_select = 0;
+    if (e->filter.on) r.pair_bytes += kFilterPairBytes;
     u64 budget = e->budget;
     if (!budget) {
         size_t fr = 0, tot = 0;
@@ -394,10 +588,14 @@ int run_export(lmat_export* e, const char* fn, int pb, bool& finer) {
     }
     r.budget = budget;
     // no pass holds more pairs than the table holds k-mers (a little slack, so that a key held twice is found and named, not refused)
-    r.cap = std::min<u64>(std::min<u64>(budget / kPairBytes, c->n_kmers + c->n_kmers / 64 + 1024), 0x7FFFFF00ull);
+    r.cap = std::min<u64>(std::min<u64>(budget / r.pair_bytes, c->n_kmers + c->n_kmers / 64 + 1024), 0x7FFFFF00ull);
     if (r.cap < 64) return xerr(e, LMAT_E_CAPACITY, "device budget of " + std::to_string(budget) + " bytes holds no pass");
     XHIP(e, ensure_all({{&r.counters, X_N * 8}, {&r.keysA, r.cap * 8}, {&r.keysB, r.cap * 8}, {&r.paysA, r.cap * 4}, {&r.paysB, r.cap * 4}, {&r.len, r.cap * 8},
                         {&r.off, (r.cap + 1) * 8}, {&r.n_runs, 8}}));
+    if (e->filter.on) {
+        XHIP(e, ensure_all({{&r.keep, r.cap * 4}, {&r.pos, r.cap * 4}}));
+        if (const int rc = r.facts()) return rc;
+    }
     XHIP(e, r.timer.init(r.st));
     Sink sink;
     sink.e = e;
@@ -411,9 +609,12 @@ int run_export(lmat_export* e, const char* fn, int pb, bool& finer) {
     const u32 n_pass = 1u << pb;
     for (u32 p = 0; p < n_pass && rc == LMAT_OK && !finer; ++p) rc = r.pass(p, sink, finer);
     e->stats.passes = n_pass;
+    // with a filter the header count is known only now
+    if (sink.f && e->filter.on && rc == LMAT_OK && !finer && (fseek(sink.f, 4, SEEK_SET) != 0 || fwrite(&sink.written, 8, 1, sink.f) != 1))
+        rc = xerr(e, LMAT_E_IO, std::string("write error on ") + fn);
     if (sink.f && fclose(sink.f) != 0 && rc == LMAT_OK && !finer) rc = xerr(e, LMAT_E_IO, std::string("write error on ") + fn);
-    if (rc == LMAT_OK && !finer && sink.written != c->n_kmers)
-        rc = xerr(e, LMAT_E_INTERNAL, "the table gave " + std::to_string(sink.written) + " records, the database counts " + std::to_string(c->n_kmers) + " k-mers");
+    if (rc == LMAT_OK && !finer && e->fstats[0] != c->n_kmers)
+        rc = xerr(e, LMAT_E_INTERNAL, "the table gave " + std::to_string(e->fstats[0]) + " records, the database counts " + std::to_string(c->n_kmers) + " k-mers");
     return rc;
 }
 
@@ -444,6 +645,84 @@ int lmat_export_set_options(lmat_export* e, uint64_t device_budget_bytes, int pr
     if (prefix_bits < -1 || prefix_bits > 2 * k || prefix_bits > 24) return xerr(e, LMAT_E_ARG, "prefix_bits must be -1 (derive) or 0 .. min(2k, 24)");
     e->budget = device_budget_bytes;
     e->prefix_bits = prefix_bits;
+    return LMAT_OK;
+}
+
+int lmat_export_set_filter(lmat_export* e, const lmat_export_filter* f) {
+    if (!e) return LMAT_E_ARG;
+    if (!f) { e->filter = lmat_export::Filter(); return LMAT_OK; }
+    lmat_ctx* c = e->ctx;
+    if (c->gene_mode) return xerr(e, LMAT_E_ARG, "a gene database holds gene ids, not taxids: its export takes no taxonomic filter");
+    if (f->mode < 0 || f->mode > LMAT_SLICE_NONE) return xerr(e, LMAT_E_ARG, "filter mode must be 0 (no taxon test), LMAT_SLICE_ANY, LMAT_SLICE_ALL or LMAT_SLICE_NONE");
+    if (f->mode && !f->n_taxa) return xerr(e, LMAT_E_ARG, "a taxon test needs at least one taxid");
+    if (!f->mode && f->n_taxa) return xerr(e, LMAT_E_ARG, "taxa without a mode: say LMAT_SLICE_ANY, LMAT_SLICE_ALL or LMAT_SLICE_NONE");
+    if (f->n_taxa && !f->taxa) return xerr(e, LMAT_E_ARG, "taxa is NULL");
+    const lmat::HostTaxonomy& T = c->tax;
+    std::vector<std::pair<u32, u32>> iv;
+    for (u32 i = 0; i < f->n_taxa; ++i) {
+        auto it = T.index_of.find(f->taxa[i]);
+        if (it == T.index_of.end()) return xerr(e, LMAT_E_TAXONOMY, "taxid " + std::to_string(f->taxa[i]) + " of the filter is not in the taxonomy tree");
+        iv.push_back(std::make_pair(T.tin[it->second], T.tout[it->second]));
+    }
+    std::sort(iv.begin(), iv.end());
+    lmat_export::Filter F;
+    for (const auto& v : iv) {   // subtrees nest or are disjoint: one that starts inside the last interval ends inside it too
+        if (!F.iv.empty() && v.first <= F.iv.back()) F.iv.back() = std::max(F.iv.back(), v.second);
+        else { F.iv.push_back(v.first); F.iv.push_back(v.second); }
+    }
+    F.mode = f->mode;
+    F.min_depth = f->min_lca_depth;
+    F.max_entries = f->max_entries;
+    F.on = F.mode || F.min_depth || F.max_entries;
+    e->filter = std::move(F);
+    return LMAT_OK;
+}
+
+int lmat_export_filter_stats(const lmat_export* e, uint64_t out6[6], double* ms_select) {
+    if (!e) return LMAT_E_ARG;
+    if (!e->done) return xerr(const_cast<lmat_export*>(e), LMAT_E_STATE, "lmat_export_run first");
+    if (out6) for (int i = 0; i < 6; ++i) out6[i] = e->fstats[i];
+    if (ms_select) *ms_select = e->ms_select;
+    return LMAT_OK;
+}
+
+// The slice goes through the ingest's own record parser as an in-memory stream of the file format, as lmat_db_build_from_genomes' result does.
+int lmat_db_from_export(lmat_ctx* dst, lmat_export* e, uint64_t table_bytes) {
+    if (!dst || !e) return LMAT_E_ARG;
+    if (dst == e->ctx) return xerr(e, LMAT_E_ARG, "the slice of a context's database cannot replace that database: give another context");
+    if (e->ctx->gene_mode) return xerr(e, LMAT_E_ARG, "a gene database is not sliced into a taxonomy context");
+    if (!dst->tax.loaded) return xerr(e, LMAT_E_STATE, "the destination context has no taxonomy loaded");
+    lmat_export_stats st;
+    int rc = lmat_export_run(e, nullptr, &st);
+    if (rc != LMAT_OK) return rc;
+    if (!st.records) return xerr(e, LMAT_E_ARG, "the slice is empty: no k-mer of the database passes the filter");
+    char* mem = nullptr;
+    size_t mem_len = 0;
+    FILE* w = open_memstream(&mem, &mem_len);
+    if (!w) return xerr(e, LMAT_E_NOMEM, "open_memstream failed");
+    Sink sink;
+    sink.e = e;
+    sink.f = w;
+    sink.h_kmers.swap(e->kmers);   // lent to the writer, handed back below
+    sink.h_tids.swap(e->tids);
+    sink.h_off.swap(e->list_off);
+    const bool ok = sink.header(e->ctx->dev.k, st.records) && sink.put(st.records);
+    e->kmers.swap(sink.h_kmers);
+    e->tids.swap(sink.h_tids);
+    e->list_off.swap(sink.h_off);
+    if (fclose(w) != 0 || !ok || !mem) { free(mem); return xerr(e, LMAT_E_NOMEM, "out of memory for the record stream"); }
+    rc = lmat_db_begin(dst, e->ctx->dev.k, 0, table_bytes);
+    if (rc == LMAT_OK) {
+        FILE* r = fmemopen(mem, mem_len, "rb");
+        if (!r) rc = lmat::set_err(dst, LMAT_E_NOMEM, "fmemopen failed");
+        else if (!dst->ingest->add_taxhisto_stream(r, "<slice of a loaded database>")) {
+            const bool tax = dst->ingest->err.compare(0, 3, "bad") == 0;   // an id the destination's taxonomy does not map
+            rc = lmat::set_err(dst, tax ? LMAT_E_TAXONOMY : LMAT_E_IO, dst->ingest->err);
+        }
+    }
+    free(mem);
+    if (rc == LMAT_OK) rc = lmat_db_finalize(dst);
+    if (rc != LMAT_OK) return xerr(e, rc, std::string("destination context: ") + lmat_last_error(dst));
     return LMAT_OK;
 }
 
