@@ -50,7 +50,7 @@ __device__ __forceinline__ void wsync() {
     else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
-static const int kGmemU = 32768;   // k-mer capacity of the global-memory class (reads up to 32787 bp)
+static const int kGmemU = 32768;   // k-mer capacity of the global-memory class (reads of up to kGmemU + k - 1 bp: 32787 at k = 20)
 static const int kGmemGrid = 2048; // its workgroups (one per-read table set of ~1.2 MB each: 2.4 GB of scratch).  Every step of a read in this class is a
                                    // round trip to memory, so what it needs is waves: 128 of them (rounds 1-3) were 8 ms per read of the heavy-tail
                                    // workload's superkingdom-wide lists (36 k such reads per 8 M: 2.2 s a launch)
@@ -2357,7 +2357,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         // (m & a) | (~m & b) is one v_bfi_b32 -- and bring the 2k bits down from the top
         auto pairswap = [](uint32_t t) -> uint32_t { return (0xAAAAAAAAu & (t << 1)) | (~0xAAAAAAAAu & (t >> 1)); };
         const uint32_t fh = pairswap(__builtin_bitreverse32((uint32_t)w)), fl = pairswap(__builtin_bitreverse32((uint32_t)(w >> 32)));
-        const uint32_t sh = 64u - 2u * (uint32_t)k;  // 24 at k = 20; k >= 16 here (the compact path's k is 10..20: see below)
+        const uint32_t sh = 64u - 2u * (uint32_t)k;  // 24 at k = 20; every k of 1..20 comes through here (both layouts), so the shift is 24..62 and always below 64
         fwd = (((uint64_t)fh << 32) | fl) >> sh;
         return ok;
     };
@@ -4706,7 +4706,7 @@ void launch_tail(const ClassifyArgs& a, hipStream_t stream) {
     else tail_kernel<16><<<grid, dim3(256), 0, stream>>>(a);
 }
 
-int classify_max_read_len() { return kGmemU + 19; }
+int classify_max_read_len(int k) { return kGmemU + (k >= 1 && k <= 20 ? k : 20) - 1; }   // P = len - k + 1 <= kGmemU
 size_t classify_gmem_scratch_bytes() { return (size_t)kGmemGrid * WL<kGmemU, 4096, 16384, true, false, true>::BYTES; }   // (the wide layout: the larger of the two)
 
 // permissive match (-s) is a compile-time variant: a run-time test of it inside the closure loops cost 22%

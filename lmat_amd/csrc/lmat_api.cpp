@@ -538,6 +538,10 @@ static int alloc_table(lmat_ctx* c, uint64_t n_kmers, uint64_t table_bytes, int 
             if (!g.nb) break;
             const double n_est = n_kmers ? (double)n_kmers : 6.4 * (double)g.nb;
             const double load = n_est / (double)g.nb;
+            // The first geometry of a caller who fixed no size has at least the buckets asked for (a load of 6.4) unless hi-space
+            // itself is smaller: 4^(k-3) buckets against up to 4^k / 2 k-mers, a dense small-k database.  The wide layout below
+            // holds those; a size the caller fixed, or one the free memory forced, stays an error.
+            if (load > 10.0 && !table_bytes && attempt == 0) break;
             if (load > 10.0) return set_err(c, LMAT_E_CAPACITY, "table_bytes (or the free device memory) too small for the number of k-mers");
             const double s0 = cpt_displaced_share(load, n_est / (0.5 * std::pow(4.0, g.m)));
             double share = s0 * (s0 > 0.15 ? 1.4 : 2.0);
@@ -1513,8 +1517,12 @@ static bool pipeline_on() {
     return on;
 }
 
+// The longest read is the one with as many k-mer positions as the global-memory class holds, so the limit moves with the loaded
+// database's k (before a database is loaded: the limit of k = 20, the largest; run_classify refuses such a context anyway).
+static int max_read_len_of(const lmat_ctx* c) { return classify_max_read_len(c->db_ready ? c->dev.k : 20); }
 static int err_read_too_long(lmat_ctx* c) {
-    return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(classify_max_read_len()) + " bases");
+    return set_err(c, LMAT_E_CAPACITY, "read longer than " + std::to_string(max_read_len_of(c)) + " bases (k = " +
+                                           std::to_string(c->db_ready ? c->dev.k : 20) + ")");
 }
 
 // ---- the stages of a launch (run_classify below), in their order ----
@@ -1662,7 +1670,7 @@ static int run_classify(lmat_ctx* c, const lmat_reads* reads, uint64_t first, ui
     if (first + count > reads->n) return set_err(c, LMAT_E_ARG, "read range out of bounds");
     if (count > 0xFFFFFFFFull) return set_err(c, LMAT_E_ARG, "batch above 2^32 reads");
     if (reads->n > 0xFFFFFFFFull) return set_err(c, LMAT_E_ARG, "read set above 2^32 reads");
-    if ((int)reads->max_len > classify_max_read_len()) return err_read_too_long(c);
+    if ((int)reads->max_len > max_read_len_of(c)) return err_read_too_long(c);
     if (c->dev.wide && !c->dev.cpt.nb) return set_err(c, LMAT_E_ARG, "a wide taxonomy needs the compact table layout (k >= 10)");
     hipSetDevice(c->device);
     int rc = prepare_set(c, count, want_cands, cand_cap, pipelined);
@@ -2466,7 +2474,7 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
     sl.reads.min_len = n ? min_len : 0;   // (the slot's records start at word 0 whatever its offsets start at: pass2 and launch_fill_offsets)
     const int used = (cn[0] != 0) + (cn[1] != 0) + (cn[2] != 0) + (cn[3] != 0);
     for (int j = 0; j < kNCls; ++j) sl.reads.cls_n[j] = used > 1 ? cn[j] : 0;
-    if ((int)max_len > classify_max_read_len()) {  // refused before anything is queued: the slot goes back untouched
+    if ((int)max_len > max_read_len_of(c)) {  // refused before anything is queued: the slot goes back untouched
         sl.state = 0;
         return err_read_too_long(c);
     }

@@ -6,6 +6,7 @@
                     TaxNodeStat::begin/next (compiled from /root/reference by oracle/Makefile -> oracle/_ref/ref_lookup)
   ref_paths.txt     TaxTree::getPathToRoot for every node of ds/tax.dat, from the reference's TaxTree
   ref_kencode.txt   kencode_c::kencode for 20-mer strings, from the reference's include/kencode.hpp
+  ref_kencode_k{9,11,17,19}.txt  the same for those strings cut to 9, 11, 17 and 19 bases
   ref_tidchecks.txt isHuman / isPhiX truth table from include/tid_checks.hpp
   ref_rkmer[_permissive].txt  per read of ds/reads.fa: valid k-mers, GC bin, marked positions, and the registered
                     taxids in registration order with their position counts, from the REFERENCE's
@@ -57,6 +58,11 @@ sf = os.path.join(here, "_strs.tmp")
 open(sf, "w").write("\n".join(strs) + "\n")
 with open(os.path.join(here, "ref_kencode.txt"), "w") as o:
     o.write(subprocess.run([os.path.join(ref, "ref_kencode"), "20", sf], capture_output=True, text=True, check=True).stdout)
+# ... and off 18/20: the same strings cut to k = 9, 11, 17 and 19 through the same encoder (tests/kmer_model.py is held to these)
+for kk in (9, 11, 17, 19):
+    open(sf, "w").write("\n".join(s[:kk] for s in strs) + "\n")
+    with open(os.path.join(here, f"ref_kencode_k{kk}.txt"), "w") as o:
+        o.write(subprocess.run([os.path.join(ref, "ref_kencode"), str(kk), sf], capture_output=True, text=True, check=True).stdout)
 os.remove(sf)
 # ---- make_db_table options: pruning (-g 2 -m rank map), human feed (-j), adaptor feed (-u)
 def decode(v, k=20):

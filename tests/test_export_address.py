@@ -63,6 +63,18 @@ def test_unaddress_inverts_address_exhaustive_k10(want):
 
 # (k, want_buckets, the bucket count the geometry must come to: 0 = not checked) -- W = hi-space / buckets
 GEOMETRIES = [
+    (11, 1, 0),                      # W = 127: hi-space 2^16 (odd k: minimizers that are their own reverse complement)
+    (11, 1 << 12, 1 << 12),          # W = 16
+    (11, (1 << 16) // 3, 0),         # W = 3
+    (13, 1, 0),                      # W = 127: hi-space 2^20
+    (13, 1 << 17, 1 << 17),          # W = 8
+    (13, (1 << 20) // 5, 0),         # W = 5
+    (15, 1, 0),                      # W = 127: hi-space 2^24
+    (15, 1 << 22, 1 << 22),          # W = 4
+    (15, (1 << 24) // 7, 0),         # W = 7
+    (17, 1, 0),                      # W = 127: hi-space 2^28
+    (17, 1 << 23, 1 << 23),          # W = 32
+    (17, (1 << 28) // 9, 0),         # W = 9
     (16, 1 << 20, 1 << 20),          # W = 64, a power of two
     (16, 1, 0),                      # W = 127, the minimum table
     (16, (1 << 26) // 3, 0),         # W = 3
