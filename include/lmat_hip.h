@@ -124,7 +124,26 @@ int lmat_db_load_image(lmat_ctx* ctx, const char* fn, uint64_t table_bytes);
  *             database streams it out of HBM, lmat_db_load_image streams it back in through pinned buffers -- the counterpart of
  *             the reference mapping its database file (src/read_label.cpp:1477-1491); lmat_db_finalize is then a no-op.  Its list
  *             records hold internal taxid indices built under the context's label modes: loading checks fingerprints of both
- *             (LMAT_E_TAXONOMY / LMAT_E_ARG on a mismatch).  table_bytes is ignored for it. */
+ *             (LMAT_E_TAXONOMY / LMAT_E_ARG on a mismatch).  table_bytes is ignored for it.
+ *             Layout (little-endian; DESIGN.md, "The device image format"; tests/img2_model.py states it in numpy): a 4 KiB header
+ *             page -- magic, version, k, the geometry of the compact table (nb, W, lowbits, m, wshift), nbuckets, ovf_nbuckets,
+ *             list_shift, n_ids, n_kmers, arena_words, n_lists, the two fingerprints, offset and size of the three sections --
+ *             then the bucket array, the overflow table and the list arena, each on a 4 KiB boundary, in that order.
+ *             VERIFIED on load, before the context gives up anything it holds (a refused image leaves its database in place):
+ *             magic and version; k; that the geometry is self-consistent (m = k - 3, lowbits, 1 <= W <= 127 >> lowbits, nb the
+ *             count W implies or the fractional form, wshift the one W implies, nbuckets = min(nb, 2^32 - 1), list_shift <= 4); that
+ *             the section sizes are what the counts imply and the sections are aligned, ordered and inside the file (bytes behind
+ *             the arena are ignored) -- LMAT_E_IO, the message names the field; then the taxonomy fingerprint (ids, depths, flags,
+ *             lineages AND the 16 -> 32 id map, through which lookups and exports translate the stored codes) with n_ids, and the
+ *             fingerprint of the label modes (-s, -g / -m, rand mode, gene mode, wide taxonomy).
+ *             NOT VERIFIED: the body.  Slot contents and arena records are trusted as written: a checksum would cost a pass over a
+ *             file whose point is to start at link rate.
+ *             A change of the layout, or of what a fingerprint covers, bumps `version`; images of another version are refused
+ *             (version 1 did not cover the id map: build such a database again from its files).  LMATIMG1 is checked against its
+ *             file by the ingest (dbbuild.cpp). */
+/* The header checks of an LMATIMG2 file alone, without a context or a device: LMAT_OK, or LMAT_E_IO with the reason in msg (up to
+ * cap bytes, NUL-terminated).  What a context adds on load are the two fingerprints and n_ids. */
+int lmat_image_check(const char* fn, char* msg, uint64_t cap);
 /* A replica of src's finalized database in dst (another GPU of the node, or the same one): the k-mer table, its
  * overflow table and the list arena are copied device to device (hipMemcpyPeer: over xGMI between GPUs), instead of
  * every GPU parsing the files again.  dst must hold the same taxonomy and label modes as src and no database yet. */

@@ -225,6 +225,7 @@ def load_library(path: str | None = None):
         "lmat_reads_upload_pairs": (i32, [vp, vp, vp, vp, vp, u64, P(vp)]),
         "lmat_stream_submit_pairs": (i32, [vp, u64, u64]),
         "lmat_stream_submit_pairs_from": (i32, [vp, vp, vp, vp, vp, u64, u64]),
+        "lmat_image_check": (i32, [cp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -257,7 +258,14 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_export_taxid_counts", "lmat_export_set_filter", "lmat_export_filter_stats", "lmat_db_from_export", "lmat_build_add_db", "lmat_table_unaddress",
             "lmat_genebuild_create", "lmat_genedb_build_from_genes",
             "lmat_debug_stream_stats", "lmat_debug_reads_words",
-            "lmat_reads_upload_pairs", "lmat_stream_submit_pairs", "lmat_stream_submit_pairs_from"]
+            "lmat_reads_upload_pairs", "lmat_stream_submit_pairs", "lmat_stream_submit_pairs_from", "lmat_image_check"]
+
+
+def image_check(path):
+    """The header checks of a device image (LMATIMG2) without a context or a device -> (code, message): (0, "") for a usable one."""
+    buf = C.create_string_buffer(1024)
+    rc = load_library().lmat_image_check(path.encode(), buf, len(buf))
+    return rc, buf.value.decode(errors="replace")
 
 
 def _ptr(a):

@@ -308,6 +308,66 @@ struct ImgHdr2 {
     uint64_t off_slots, bytes_slots, off_ovf, bytes_ovf, off_arena, bytes_arena;
 };
 static_assert(sizeof(ImgHdr2) <= 4096, "header page");
+// Bumped by every change of the layout (header, bucket, slot, list record) and of what the fingerprints cover; tests/img2_model.py
+// states the layout of the current version and changes in the same commit.  2: the taxonomy fingerprint covers the 16 -> 32 map.
+const uint32_t kImgVersion = 2;
+// Everything the loader and the kernels take from the header, checked against the file size and against itself before any of it
+// is used: a field that passes cannot make cpt_address index past the bucket array or a list payload past the arena's end (the
+// BODY -- slot contents, arena records -- is trusted: a checksum would cost a pass over a file whose point is to start at link
+// rate).  The geometry must be self-consistent, not "what cpt_geometry gives for nb": cpt_geometry(k, nb) need not give back the
+// W that produced nb.  No HIP calls.  false: msg names the field.
+bool image_header_check(const ImgHdr2& h, uint64_t fsz, std::string& msg) {
+    auto bad = [&](const std::string& m) { msg = m; return false; };
+    auto num = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+    if (memcmp(h.magic, "LMATIMG2", 8) != 0) return bad("magic: not a device image");
+    if (h.version == 1) return bad("version 1: an image written before the taxonomy fingerprint covered the 16-bit map cannot prove which map its lists were stored under: build the database again from its files");
+    if (h.version != kImgVersion) return bad("version " + num(h.version) + ": this engine reads version " + num(kImgVersion));
+    if (h.k < 1 || h.k > 20) return bad("k = " + num(h.k) + ": not in 1..20");
+    if (h.list_shift > (uint32_t)kListShiftMax) return bad("list_shift = " + num(h.list_shift) + ": above " + num(kListShiftMax));
+    if (!h.nb) {  // wide layout: no compact geometry
+        if (h.W || h.lowbits || h.m || (h.wshift != -1 && h.wshift != 0)) return bad("W / lowbits / m / wshift: set in an image of the wide layout (nb = 0)");
+        if (h.nbuckets < 16) return bad("nbuckets = " + num(h.nbuckets) + ": a wide table has at least 16 buckets");
+    } else {
+        if (h.k < 10) return bad("nb: k = " + num(h.k) + " has no compact layout");
+        const uint32_t m = h.k - (kCptW - 1), lowbits = 2 * m > 32 ? 2 * m - 32 : 0;
+        if (h.m != m) return bad("m = " + num(h.m) + ": k - 3 is " + num(m));
+        if (h.lowbits != lowbits) return bad("lowbits = " + num(h.lowbits) + ": " + num(lowbits) + " at this k");
+        if (h.W < 1 || h.W > (127u >> lowbits)) return bad("W = " + num(h.W) + ": not in 1.." + num(127u >> lowbits));
+        const uint64_t space = 1ull << (2 * m - lowbits);
+        if (h.wshift == -2) {
+            if (space != (1ull << 32)) return bad("wshift = -2: a fractional width needs a 32-bit hi-space (k >= 19)");
+            if (h.nb <= (1ull << 30) || h.nb >= (1ull << 32)) return bad("nb = " + num(h.nb) + ": a fractional width has between 2^30 and 2^32 buckets");
+            if (h.W != (space + h.nb - 1) / h.nb) return bad("W = " + num(h.W) + ": nb makes it " + num((space + h.nb - 1) / h.nb));
+        } else {
+            if (h.nb != (space + h.W - 1) / h.W) return bad("nb = " + num(h.nb) + ": W makes it " + num((space + h.W - 1) / h.W));
+            const int ws = (h.W & (h.W - 1)) == 0 ? 31 - __builtin_clz(h.W) : -1;
+            if (h.wshift != ws) return bad("wshift = " + std::to_string(h.wshift) + ": W makes it " + std::to_string(ws));
+        }
+        if (h.nbuckets != std::min<uint64_t>(h.nb, 0xFFFFFFFFull)) return bad("nbuckets = " + num(h.nbuckets) + ": nb makes it " + num(std::min<uint64_t>(h.nb, 0xFFFFFFFFull)));
+    }
+    if (h.bytes_slots != (h.nb ? h.nb : (uint64_t)h.nbuckets) * 64) return bad("bytes_slots = " + num(h.bytes_slots) + ": the bucket count makes it " + num((h.nb ? h.nb : (uint64_t)h.nbuckets) * 64));
+    if (h.bytes_ovf != (uint64_t)h.ovf_nbuckets * 64) return bad("bytes_ovf = " + num(h.bytes_ovf) + ": ovf_nbuckets makes it " + num((uint64_t)h.ovf_nbuckets * 64));
+    if (h.arena_words > (1ull << 40) || h.bytes_arena != h.arena_words * 2) return bad("bytes_arena = " + num(h.bytes_arena) + " against arena_words = " + num(h.arena_words));
+    // sections: on 4 KiB boundaries, in order, none inside another, all inside the file (each sum is of two numbers below 2^62)
+    if (fsz >= (1ull << 62)) return bad("file size");
+    if (h.off_slots % 4096 || h.off_slots < 4096 || h.off_slots > fsz) return bad("off_slots = " + num(h.off_slots) + ": not a 4 KiB boundary behind the header page and inside the file");
+    if (h.off_ovf % 4096 || h.off_ovf > fsz || h.off_ovf < h.off_slots + h.bytes_slots) return bad("off_ovf = " + num(h.off_ovf) + ": not a 4 KiB boundary behind the bucket array and inside the file");
+    if (h.off_arena % 4096 || h.off_arena > fsz || h.off_arena < h.off_ovf + h.bytes_ovf) return bad("off_arena = " + num(h.off_arena) + ": not a 4 KiB boundary behind the overflow table and inside the file");
+    if (h.off_arena + h.bytes_arena > fsz) return bad("file size " + num(fsz) + ": the arena ends at " + num(h.off_arena + h.bytes_arena) + " (truncated)");
+    return true;
+}
+// reads and checks the header page of fn; LMAT_E_IO with msg set when the file is not a usable device image
+int image_header_read(const char* fn, ImgHdr2& h, std::string& msg) {
+    const int fd = open(fn, O_RDONLY);
+    if (fd < 0) { msg = std::string("cannot read database image ") + fn; return LMAT_E_IO; }
+    struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+    const off_t fsz = lseek(fd, 0, SEEK_END);
+    std::vector<char> page(4096, 0);
+    if (fsz < 4096 || pread(fd, page.data(), 4096, 0) != 4096) { msg = std::string("database image ") + fn + ": shorter than its header page"; return LMAT_E_IO; }
+    memcpy(&h, page.data(), sizeof h);
+    if (!image_header_check(h, (uint64_t)fsz, msg)) { msg = std::string("database image ") + fn + ": " + msg; return LMAT_E_IO; }
+    return LMAT_OK;
+}
 uint64_t fnv(uint64_t h, const void* p, size_t n) {
     const unsigned char* b = (const unsigned char*)p;
     for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 0x100000001B3ull; }
@@ -320,6 +380,9 @@ uint64_t tax_fingerprint(const lmat_ctx* c) {
     const HostTaxonomy& T = c->tax;
     uint64_t h = 0xCBF29CE484222325ull;
     h = fnv_vec(h, T.tid32); h = fnv_vec(h, T.fdepth); h = fnv_vec(h, T.flags); h = fnv_vec(h, T.paths); h = fnv_vec(h, T.path_len);
+    // the arena keeps the stored 16-bit codes of every list, and lookups and the export translate them through the context's map
+    // (tb.conv): the same tree under another -f map would answer with other taxids
+    h = fnv_vec(h, T.conv);
     return h;
 }
 uint64_t mode_fingerprint(const lmat_ctx* c) {
@@ -385,7 +448,7 @@ int save_device_image(lmat_ctx* c, const char* fn) {
     ImgHdr2 h;
     memset(&h, 0, sizeof h);
     memcpy(h.magic, "LMATIMG2", 8);
-    h.version = 1; h.k = (uint32_t)D.k;
+    h.version = kImgVersion; h.k = (uint32_t)D.k;
     h.nb = D.cpt.nb; h.W = D.cpt.W; h.lowbits = (uint32_t)D.cpt.lowbits; h.m = (uint32_t)D.cpt.m; h.wshift = D.cpt.wshift;
     h.nbuckets = D.nbuckets; h.ovf_nbuckets = D.ovf_nbuckets; h.list_shift = D.list_shift; h.n_ids = D.n_ids;
     h.n_kmers = c->n_kmers; h.arena_words = c->arena_words; h.n_lists = c->n_lists;
@@ -411,22 +474,20 @@ int save_device_image(lmat_ctx* c, const char* fn) {
 }
 int load_device_image(lmat_ctx* c, const char* fn) {
     if (c->gene_mode) return set_err(c, LMAT_E_ARG, "device images hold taxonomy databases");
+    // every refusal comes before anything of the context is freed: a refused image leaves the database the context holds in place
+    ImgHdr2 h;
+    std::string msg;
+    if (image_header_read(fn, h, msg) != LMAT_OK) return set_err(c, LMAT_E_IO, msg);
+    if (h.tax_fingerprint != tax_fingerprint(c) || h.n_ids != c->dev.n_ids)
+        return set_err(c, LMAT_E_TAXONOMY, "the image was saved under a different taxonomy or 16-bit id map (its list records hold that taxonomy's internal ids and that map's codes): load the files it was built with");
+    if (h.mode_fingerprint != mode_fingerprint(c))
+        return set_err(c, LMAT_E_ARG, "the image was saved under different label modes (-s / -g / -m shape the list records): set the same modes, or build from the tax_histo files");
     const int fd = open(fn, O_RDONLY);
     if (fd < 0) return set_err(c, LMAT_E_IO, std::string("cannot read database image ") + fn);
     struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
-    std::vector<char> page(4096, 0);
-    ImgHdr2 h;
-    if (pread(fd, page.data(), 4096, 0) != 4096) return set_err(c, LMAT_E_IO, std::string("cannot read database image ") + fn);
-    memcpy(&h, page.data(), sizeof h);
-    if (memcmp(h.magic, "LMATIMG2", 8) != 0 || h.version != 1 || h.k < 1 || h.k > 20) return set_err(c, LMAT_E_IO, "not a device image of this engine version");
-    if (h.tax_fingerprint != tax_fingerprint(c) || h.n_ids != c->dev.n_ids)
-        return set_err(c, LMAT_E_TAXONOMY, "the image was saved under a different taxonomy (its list records hold that taxonomy's internal ids): load the files it was built with");
-    if (h.mode_fingerprint != mode_fingerprint(c))
-        return set_err(c, LMAT_E_ARG, "the image was saved under different label modes (-s / -g / -m shape the list records): set the same modes, or build from the tax_histo files");
-    const off_t fsz = lseek(fd, 0, SEEK_END);
-    if (fsz < 0 || (uint64_t)fsz < h.off_arena + h.bytes_arena || h.bytes_slots % 64 || h.bytes_ovf != (uint64_t)h.ovf_nbuckets * 64 ||
-        h.bytes_slots != (h.nb ? h.nb : (uint64_t)h.nbuckets) * 64 || h.bytes_arena != h.arena_words * 2)
-        return set_err(c, LMAT_E_IO, "database image truncated or inconsistent");
+    delete c->ingest;
+    c->ingest = nullptr;
+    sb_free(c);
     hipSetDevice(c->device);
     DeviceTables& D = c->dev;
     if (D.slots) { hipFree(D.slots); D.slots = nullptr; }
@@ -469,27 +530,24 @@ int lmat_db_load_image(lmat_ctx* c, const char* fn, uint64_t table_bytes) {
         FILE* f = fopen(fn, "rb");
         const bool img2 = f && fread(magic, 8, 1, f) == 1 && memcmp(magic, "LMATIMG2", 8) == 0;
         if (f) fclose(f);
-        if (img2) {
-            delete c->ingest;
-            c->ingest = nullptr;
-            sb_free(c);
-            return load_device_image(c, fn);
-        }
+        if (img2) return load_device_image(c, fn);   // (gives up the context's database only once the header has passed)
+    }
+    uint32_t kk = 0;
+    uint64_t n = 0;
+    {   // header first, before the context gives up what it holds: the table is sized from the image's k-mer count, then the arrays stream through in chunks
+        FILE* f = fopen(fn, "rb");
+        char magic[8];
+        const bool ok = f && fread(magic, 8, 1, f) == 1 && memcmp(magic, "LMATIMG1", 8) == 0 && fread(&kk, 4, 1, f) == 1 && fread(&n, 8, 1, f) == 1;
+        if (f) fclose(f);
+        if (!ok) return set_err(c, LMAT_E_IO, std::string("cannot read database image ") + fn);
+        if (kk < 1 || kk > 20) return set_err(c, LMAT_E_IO, "image holds an unsupported k-mer length");
     }
     delete c->ingest;
     c->ingest = new Ingest();
     c->ingest_table_bytes = table_bytes;
     c->db_ready = false;
     sb_free(c);
-    {   // header first: the table is sized from the image's k-mer count, then the arrays stream through in chunks
-        FILE* f = fopen(fn, "rb");
-        char magic[8];
-        uint32_t kk = 0;
-        uint64_t n = 0;
-        const bool ok = f && fread(magic, 8, 1, f) == 1 && memcmp(magic, "LMATIMG1", 8) == 0 && fread(&kk, 4, 1, f) == 1 && fread(&n, 8, 1, f) == 1;
-        if (f) fclose(f);
-        if (!ok) return set_err(c, LMAT_E_IO, std::string("cannot read database image ") + fn);
-        if (kk < 1 || kk > 20) return set_err(c, LMAT_E_IO, "image holds an unsupported k-mer length");
+    {
         int rc = sb_begin(c, n, table_bytes, (int)kk);
         if (rc) return rc;
     }
@@ -2621,6 +2679,19 @@ int lmat_debug_stream_stats(const lmat_stream* st, uint64_t* out6) {
     const uint64_t v[6] = {st->n_uniform, st->n_general, st->n_threaded, st->n_cls_sent, st->n_grow, cap};
     for (int i = 0; i < 6; ++i) out6[i] = v[i];
     return LMAT_OK;
+}
+
+int lmat_image_check(const char* fn, char* msg, uint64_t cap) {
+    if (!fn) return LMAT_E_ARG;
+    ImgHdr2 h;
+    std::string m;
+    const int rc = image_header_read(fn, h, m);
+    if (msg && cap) {
+        const uint64_t n = std::min<uint64_t>(m.size(), cap - 1);
+        memcpy(msg, m.data(), n);
+        msg[n] = 0;
+    }
+    return rc;
 }
 
 int lmat_table_address(int k, uint64_t want_buckets, uint64_t kmer, uint64_t* n_buckets, uint32_t* bucket, uint32_t* tag) {

@@ -1123,6 +1123,23 @@ def test_device_image_round_trip(tmp_path, small_dataset):
     img = str(tmp_path / "db.img2")
     a.save_device_image(img)
     assert open(img, "rb").read(8) == b"LMATIMG2" and os.path.getsize(img) >= a.table_bytes + a.arena_bytes
+    # the header against the format stated in img2_model.py (frame and geometry: the minimum table of k = 20, two low bits in the
+    # tag), and the dataset's own buckets read straight from the file -- the other 8 GB are not decoded
+    import dbgen_model
+    import img2_model
+    h = img2_model.check(img, body=False)
+    assert (h.k, h.lowbits, h.m, h.W, h.wshift, h.nb) == (20, 2, 17, 31, -1, -(-(1 << 32) // 31))
+    assert h.n_kmers == a.db_size and h.bytes_slots + h.bytes_ovf == a.table_bytes and h.bytes_arena == a.arena_bytes
+    recs = dbgen_model.read_taxhisto(ds["db"])[2]
+    canon = np.array([km for km, _ in recs], dtype=np.uint64)
+    canon = canon[canon <= img2_model.revcomp(canon, 20)]                   # (the buckets hold canonical words only)
+    found, pay, spilled = img2_model.probe_buckets(img, canon)
+    assert found.sum() > 0.9 * canon.size and (found | spilled).all()       # in its home bucket under its tag, or the bucket says where else
+    n_list = {km: len(l) for km, l in recs}
+    many = np.array([n_list[int(x)] > 1 for x in canon[found].tolist()])
+    lp = pay[found]
+    assert (lp[many] >= 65536).all() and ((lp[many] - np.uint64(65536)) * np.uint64(16 << h.list_shift) < np.uint64(h.bytes_arena)).all()
+    assert ((lp[~many] >= 1) & ((lp[~many] < min(h.n_ids, 65536)) | ((lp[~many] >= 65536) & ((lp[~many] - np.uint64(65536)) * np.uint64(16 << h.list_shift) < np.uint64(h.bytes_arena))))).all()
     rng = np.random.default_rng(5)
     kms = rng.integers(0, 1 << 40, 4000, dtype=np.uint64)
     b = Engine(0, Params.run_rl())
