@@ -1090,6 +1090,13 @@ class Engine:
         self._chk(self.lib.lmat_debug_last_counters(self.ctx, _ptr(out)))
         return {"past_fast": int(out[2]), "past_e512": int(out[3]), "past_middle": int(out[10]), "past_large": int(out[7])}
 
+    def closure_stride_taken(self):
+        """-> reads of the last launch whose closure walked its chains at a fixed stride (kernels.hip classify_one).  Counted only by
+        launches made under LMAT_CLOSURE_STRIDE=2, which run the generic kernel; 0 otherwise."""
+        out = np.zeros(16, dtype=np.uint32)
+        self._chk(self.lib.lmat_debug_last_counters(self.ctx, _ptr(out)))
+        return int(out[12])
+
     def variant_launches(self):
         """-> launches of the 160-k-mer fast class on this engine's device so far, by kernel: {"generic": n, "plain": n} (LMAT_PLAIN)."""
         out = np.zeros(2, dtype=np.uint64)

@@ -21,6 +21,12 @@
 #define STOP_AT(n, v) do { if (LMAT_ABLATE && A.prm.stop_after == (n)) { if (lane == 0) { emit(250, (v)); } return; } } while (0)
 #ifndef LMAT_CLOSURE_FAST
 #define LMAT_CLOSURE_FAST 1   // (A/B builds: -DLMAT_CLOSURE_FAST=0)
+#ifndef LMAT_CLOSURE_STRIDE
+#define LMAT_CLOSURE_STRIDE 1        // (A/B builds: -DLMAT_CLOSURE_STRIDE=0: no walk at a fixed stride; at run time LMAT_CLOSURE_STRIDE=0)
+#endif
+#ifndef LMAT_CLOSURE_STRIDE_MASKS
+#define LMAT_CLOSURE_STRIDE_MASKS 1  // (A/B builds: -DLMAT_CLOSURE_STRIDE_MASKS=0: the strided walk alone, step (3a) as in the general steps)
+#endif
 #endif
 #ifndef LMAT_LIST_INLINE
 #define LMAT_LIST_INLINE 1    // (A/B builds: -DLMAT_LIST_INLINE=0: lists of three kept ids wait for K3b stage 2, two scans in stage 1)
@@ -1332,6 +1338,11 @@ __device__ uint32_t g_tie_why[32];
 // with one left were lists of up to 3 / 4 / 6 ids inside the staged window completed in stage 1, [8 .. 14] distinct lists by kept
 // count: 1, 2, 3, 4, 5..6, 7..14, above 14, [15] empty lists (scripts/list_share.py reads them through lmat_ablate_list_share)
 __device__ uint32_t g_list_share[16];
+// ablation builds: what the closure of the T <= 64 classes meets, counted across launches -- [0] reads that reach it, [1] with one eligible
+// slot (`one`), [2] with several and a walk (W > 0); of [2]: [4 .. 10] 2 .. 8 walked chains, [11] more, [12 .. 15] the longest walked
+// chain <= 8, <= 16, <= 32, longer, [16] / [17] nel <= 64 / above, [18] meeting every entry condition of the fixed-stride walk
+// (DESIGN §3, item 4), [19] the same at a stride fixed to 8 (scripts/closure_stride_share.py reads them through lmat_ablate_stride_share)
+__device__ uint32_t g_stride_share[32];
 #endif
 // Tied ids at the top, decided in closed form: what k4_wave_path turns away for "another id with a count >= c0".
 // Of the closure the number of kept slots is asked, as there (chain = kept << 8 | 1 << 17 | 1 << 18).  c0 = the largest kept count,
@@ -3375,6 +3386,13 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         }
         WSYNC();
     }
+    if constexpr (PLAIN && sizeof(ent_t) == 4 && (2 * L::TH) % 256 == 0 && (L::OFF_R1 + 8 * T) % 16 == 0 && sizeof(tid_t) == 2) {
+        // hent and best lie back to back behind reg, stamp, cnt and leaf (8 T bytes): cleared 16 bytes a lane and store.  (The plain
+        // variants only: the four zero registers cost the generic instantiations that sit at their 64-register cap a vector spill.)
+        static_assert(L::OFF_R1 % 16 == 0 && (8 * T) % 16 == 0, "16-byte LDS stores");
+        u32x4* z = (u32x4*)hent;
+        for (int i = lane; i < 2 * L::TH / 4; i += 64) z[i] = u32x4{0u, 0u, 0u, 0u};
+    } else
     for (int i = lane; i < L::TH; i += 64) { hent[i] = 0; best[i] = 0; }  // (behind the list window, which lies under these tables)
     WSYNC();
     if constexpr (INK4) {
@@ -3594,35 +3612,108 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         const uint64_t todo0 = __ballot(first[lane] != 0xFFFFFFFFu);
         const bool one = LMAT_CLOSURE_FAST && todo0 != 0 && (todo0 & (todo0 - 1)) == 0;
         const int sx0 = one ? __builtin_ctzll(todo0) : 0;
+#if LMAT_ABLATE
+        if (!PERM) {   // what the fixed-stride closure would meet (g_stride_share, scripts/closure_stride_share.py)
+            uint32_t nch_a = 0, mx_a = 0;
+#pragma unroll
+            for (int ch = 0; ch < EC; ++ch) {
+                const uint32_t e = (uint32_t)ch * 64 + lane;
+                const uint32_t sl = sreg[ch] & 0xFFu;
+                const uint32_t plen = lane_of(f_plen, sl);
+                const bool walk = e < nel && first[sl] == e;
+                nch_a += popc64(__ballot(walk));
+                mx_a = max(mx_a, wave_max_u32(walk ? plen : 0u));
+            }
+            uint32_t S_a = 1;
+            while (S_a < mx_a) S_a <<= 1;
+            if (lane == 0) {
+                atomicAdd(&g_stride_share[0], 1u);
+                if (one) atomicAdd(&g_stride_share[1], 1u);
+                if (!one && mx_a > 0) {
+                    atomicAdd(&g_stride_share[2], 1u);
+                    atomicAdd(&g_stride_share[nch_a <= 8u ? 2u + nch_a : 11u], 1u);   // [4 .. 10]: 2 .. 8 walked chains, [11]: more ([3]: one, the rest of its W empty)
+                    atomicAdd(&g_stride_share[mx_a <= 8u ? 12 : (mx_a <= 16u ? 13 : (mx_a <= 32u ? 14 : 15))], 1u);
+                    atomicAdd(&g_stride_share[nel <= 64u ? 16 : 17], 1u);
+                    if (nel <= 64u && nch_a * S_a <= 64u) atomicAdd(&g_stride_share[18], 1u);
+                    if (nel <= 64u && nch_a * 8u <= 64u && mx_a <= 8u) atomicAdd(&g_stride_share[19], 1u);
+                }
+            }
+        }
+#endif
+        // Several eligible slots whose chains fit the wave side by side at one stride: nch chains, one per slot of
+        // todo0 (a slot has exactly one first eligible element), each given S = 2^lgS lanes, S the largest power of two with
+        // nch * S <= 64; taken when no walked chain is longer than S and the elements are one chunk.  That is the same set of reads
+        // as "the smallest power of two that holds the longest chain, times nch, is at most 64" -- a power of two that fits fits
+        // under the largest one that does -- and it asks one compare of the chain lengths instead of their maximum.  Item lane i
+        // then serves entry i & (S - 1) of chain i >> lgS: no offsets to scan, no search per item, and the ancestor masks of
+        // step (3a) come out of the walk itself.  A launch-wide bit allows it (KernelParams::k4_chain bit 3, LMAT_CLOSURE_STRIDE=0
+        // clears it; PLAIN has it set).  Anything else takes the general steps unchanged.
+        bool strided = false;
+        uint32_t lgS = 0, nch = 0;
+        uint16_t* rk = el_off;   // [nch] slot | chain length << 8 of the walked elements, in element order (the strided walk writes no offsets)
         if (one) {
             W = (uint32_t)__builtin_amdgcn_readlane((int)f_plen, sx0);
         } else {
+            if (LMAT_CLOSURE_STRIDE && !PERM && (PLAIN || (A.prm.k4_chain & 8)) && nel <= 64u) {   // (-s: nothing is eligible, no closure)
+                nch = (uint32_t)popc64(todo0);
+                lgS = nch > 1u ? 6u - (32u - (uint32_t)__builtin_clz(nch - 1u)) : 0u;   // (one chain is `one`: nch is 0 or at least 2 here, lgS at most 5)
+                strided = (__ballot(f_plen > (1u << lgS)) & todo0) == 0;
+            }
+            if (strided) {
+                // Every walked element writes its slot and chain length at its rank among the walked elements: element order, which is
+                // the order of the dense item list below.  W: nothing on this path reads the sum of the chain lengths (`lone` asks
+                // `one`, an item list of at most 64 never passes 65535, the loop below makes one pass), only whether there is anything
+                // to walk; ablation builds report the sum at stop 44 as the general steps do.
+                const uint32_t sl = sreg[0] & 0xFFu;
+                const uint32_t plen = lane_of(f_plen, sl);
+                const bool walk = (uint32_t)lane < nel && first[sl] == (uint32_t)lane;
+                const uint64_t WM = __ballot(walk);
+                if (walk) {
+                    rk[prefix_count(WM)] = (uint16_t)(sl | (plen << 8));
+                    if (LMAT_CLOSURE_STRIDE_MASKS) anc_zw[sl] = u32x2{0u, 0u};   // the chain's ancestor mask, gathered by the walk below
+                }
+                if (LMAT_ABLATE) W = wave_sum(walk ? plen : 0u);
+                else W = (uint32_t)popc64(__ballot(f_plen != 0u) & todo0);   // (the walked chains that are not empty: a scalar count, not a select in a vector register)
+#if !LMAT_ABLATE
+                if (!PLAIN && (A.prm.k4_chain & 16) && lane == 0) G_ADD(&g_cursor[kCurStrideTaken], 1u);   // (the tests' count of the reads that came this way: LMAT_CLOSURE_STRIDE=2)
+#endif
+            } else {
 #pragma unroll
-            for (int ch = 0; ch < EC; ++ch) {
-                if ((uint32_t)ch * 64 < nel) {
-                    const uint32_t e = (uint32_t)ch * 64 + lane;
-                    const uint32_t sl = sreg[ch] & 0xFFu;
-                    const uint32_t plen = lane_of(f_plen, sl);
-                    const bool walk = e < nel && first[sl] == e;
-                    const uint32_t w = walk ? plen : 0u;
-                    const uint32_t incl = wave_scan_incl(w);
-                    if (e < nel) el_off[e] = (uint16_t)(W + incl - w);
-                    W += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                for (int ch = 0; ch < EC; ++ch) {
+                    if ((uint32_t)ch * 64 < nel) {
+                        const uint32_t e = (uint32_t)ch * 64 + lane;
+                        const uint32_t sl = sreg[ch] & 0xFFu;
+                        const uint32_t plen = lane_of(f_plen, sl);
+                        const bool walk = e < nel && first[sl] == e;
+                        const uint32_t w = walk ? plen : 0u;
+                        const uint32_t incl = wave_scan_incl(w);
+                        if (e < nel) el_off[e] = (uint16_t)(W + incl - w);
+                        W += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                    }
                 }
             }
             WSYNC();
         }
         STOP_AT(44, W);
         if (W > 65535u) overflow = true;  // item offsets are u16; such a read goes to the large-capacity kernel
+        // (the strided walk: one pass.  Lane order is (chain in element order, then path position) -- the relative order of the dense
+        //  item list, which on such a read is one pass of at most 64 items too --, the lowest lane of an id registers it, and the
+        //  new slots are handed out by the rank among those lanes: every new ancestor gets the slot the general steps give it.)
         for (uint32_t i0 = 0; i0 < W && !overflow; i0 += 64) {
             const uint32_t i = i0 + lane;
-            const bool act = i < W;
+            bool act = i < W;
             uint32_t a = 0, h = 0;
             uint64_t pe = 0;
             uint32_t sl_i = 0, rel = 0;
             if (one) {
                 sl_i = (uint32_t)sx0;
                 rel = i;
+            } else if (strided) {
+                const uint32_t c = (uint32_t)lane >> lgS;
+                const uint32_t ent = c < nch ? (uint32_t)rk[c] : 0u;   // (a lane past the last chain: length 0)
+                sl_i = ent & 0xFFu;
+                rel = (uint32_t)lane & ((1u << lgS) - 1u);
+                act = rel < (ent >> 8);
             } else if (act) {
                 uint32_t lo = 0, hi = nel;  // last element whose offset is <= i (offsets are non-decreasing)
                 while (lo < hi) {
@@ -3643,7 +3734,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
                 atomicMin(&hent[h], a | ((0x8000u | (uint32_t)lane) << 16));
             }
             WSYNC();
-            const uint64_t nm_ = __ballot(i < W) & __ballot((hent[h] >> 16) == (0x8000u | (uint32_t)lane));
+            const uint64_t nm_ = __ballot(act) & __ballot((hent[h] >> 16) == (0x8000u | (uint32_t)lane));
             const uint32_t newcnt = popc64(nm_);
             if (nT + newcnt > (uint32_t)T) { overflow = true; break; }
             if (lane_bit(nm_)) {
@@ -3654,6 +3745,23 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             }
             nT += newcnt;
             WSYNC();
+            if (LMAT_CLOSURE_STRIDE_MASKS && strided) {
+                // Step (3a) from the walk.  The registered proper ancestors of a kept id are exactly the entries of its path: a path
+                // holds every node above its id up to the root and never the id itself (taxonomy.cpp), "a above x" by the Euler
+                // intervals of (3a) is "a is on x's path" (build_euler_intervals: every tin is unique, the test is strict, so an id is
+                // not above itself there either), and every entry has just been registered or found -- kept ids among them, with the
+                // slots phase 1 gave them.  So the OR of 1 << slot over a chain's item lanes is the mask (3a) computes for the chain's
+                // id: OR-ed together in the chain's own slot of the fact-word array, whose entries below nT_p1 nobody uses (the
+                // closure registers from nT_p1 up; the chains' ids are kept ids, below it).
+                // (One LDS OR per item lane into the half of the chain's mask that holds its slot's bit, as step (3b) ORs its masks
+                //  together; the walked elements cleared the masks when they wrote their ranks.  An OR across each group of S lanes
+                //  by DPP row operations was built first: with the stride a run-time scalar it compiled to a compare and a branch
+                //  per step and word, and executed 24 vector instructions a read MORE than step (3a) -- DESIGN section 6.)
+                if (act) {
+                    const uint32_t s_i = hent[h] >> 16;
+                    __hip_atomic_fetch_or((unsigned int*)anc_zw + 2u * sl_i + (s_i >> 5), 1u << (s_i & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
         }
         STOP_AT(45, nT);
         // What the decision step wants of the ids the closure registered -- interval, depth, flags -- came with their path entries:
@@ -3678,7 +3786,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             // (3a) for every kept id that is eligible somewhere: the set of slots that are proper ancestors of it, as a
             //      64-bit mask held by the id's own lane
             uint32_t anc_lo = 0, anc_hi = 0;
-            uint64_t todo = todo0;
+            uint64_t todo = LMAT_CLOSURE_STRIDE_MASKS && strided ? 0ull : todo0;   // (the strided walk left the masks in LDS, by slot)
             while (todo) {
                 const int sx = __builtin_ctzll(todo);
                 todo &= todo - 1;
@@ -3708,7 +3816,9 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
                     const uint32_t e = (uint32_t)ch * 64 + lane;
                     const uint32_t se = e < nel ? (uint32_t)el_ta[e] : 0u;  // slot | eligible << 8 (stored above)
                     const uint32_t sl = se & 0xFFu;
-                    const uint32_t alo = lane_of(anc_lo, sl), ahi = wide_t ? lane_of(anc_hi, sl) : 0u;
+                    uint32_t alo, ahi;
+                    if (LMAT_CLOSURE_STRIDE_MASKS && strided) { const u32x2 am = anc_zw[sl]; alo = am.x; ahi = am.y; }  // (read by every lane; used by the eligible elements, whose slots were walked)
+                    else { alo = lane_of(anc_lo, sl); ahi = wide_t ? lane_of(anc_hi, sl) : 0u; }
                     if (e < nel) {
                         const uint32_t d2 = 2u * (uint32_t)el_d[e];
                         __hip_atomic_fetch_or(&memw[d2 + (sl >> 5)], 1u << (sl & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -4592,7 +4702,7 @@ static int k4_static_of(const ClassifyArgs& a) {
 static bool plain_launch(const ClassifyArgs& a, int k4_static) {
     static const bool on = !LMAT_ABLATE && (!getenv("LMAT_PLAIN") || atoi(getenv("LMAT_PLAIN")) != 0);
     return on && a.tb.k == 20 && a.tb.cpt.nb && a.tb.cpt.m == 17 && a.tb.cpt.lowbits == 2 && !a.tb.wide && !a.nm.active && !a.rand_max &&
-           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 29 && !a.cands && a.prm.hbias == 0.0f &&
+           !a.gene_mode && !a.prm.permissive && a.prm.stop_after == 0 && k4_static == 29 && (a.prm.k4_chain & 24) == 8 && !a.cands && a.prm.hbias == 0.0f &&
            a.p_min == 0 && a.p_max == 0xFFFFFFFFu && !a.index && !a.count_ptr && a.tail_lpr == 4;
 }
 // The plain run over records of one geometry (classify_one's UNI): a.uniform is the host's word that every read of the launch has
@@ -4692,6 +4802,12 @@ extern "C" int lmat_ablate_list_share(uint32_t* out16, int reset) {   // K3b sta
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(lmat::g_list_share), 64) != hipSuccess) return -1;
     if (reset) { const uint32_t z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lmat::g_list_share), z, 64) != hipSuccess) return -1; }
+    return 0;
+}
+extern "C" int lmat_ablate_stride_share(uint32_t* out32, int reset) {   // the closure's chains (g_stride_share; scripts/closure_stride_share.py)
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(lmat::g_stride_share), 128) != hipSuccess) return -1;
+    if (reset) { const uint32_t z[32] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lmat::g_stride_share), z, 128) != hipSuccess) return -1; }
     return 0;
 }
 namespace lmat {

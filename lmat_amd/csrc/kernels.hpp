@@ -81,6 +81,7 @@ enum CursorWord {
     kCurChainTaken = 13,// ... of them those the closed form decided (k4_wave_chain),
     kCurPathSeen = 14,  // ... of the rest those offered to the closed form for one dominant lineage (the closure finished),
     kCurPathTaken = 1,  // ... of them those it decided (k4_wave_path)
+    kCurStrideTaken = 12, // production builds, launches with bit 4 of KernelParams::k4_chain (LMAT_CLOSURE_STRIDE=2): reads whose closure walked at a fixed stride
     kCurBatchErr = 15, // error flags of a batch that keeps its own (the streamed boundary) instead of the sticky word
 };
 

@@ -105,6 +105,12 @@ static KernelParams kparams(const lmat_params& p) {
     if (!(getenv("LMAT_K4_PATH") && atoi(getenv("LMAT_K4_PATH")) == 0)) k.k4_chain |= 2;
     // LMAT_K4_TIE=0: the same for reads with tied ids at the top (k4_wave_tie): bit 2
     if (!(getenv("LMAT_K4_TIE") && atoi(getenv("LMAT_K4_TIE")) == 0)) k.k4_chain |= 4;
+    // LMAT_CLOSURE_STRIDE=0: the closure of a read with several eligible ids takes its general steps, not the walk at a fixed stride
+    // (kernels.hip classify_one): bit 3.  The plain-run variant has the walk compiled in, so such a run takes the
+    // generic kernel, as with LMAT_K4_CHAIN=0.  LMAT_CLOSURE_STRIDE=2 (tests): on, and the generic kernel counts the reads that take
+    // it into word kCurStrideTaken of the launch's counter block (bit 4).
+    if (const char* cs = getenv("LMAT_CLOSURE_STRIDE")) k.k4_chain |= atoi(cs) == 0 ? 0 : (atoi(cs) == 2 ? 24 : 8);
+    else k.k4_chain |= 8;
     k.k4_static = 0;
     return k;
 }

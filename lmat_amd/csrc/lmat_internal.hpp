@@ -106,7 +106,9 @@ struct KernelParams {
     int k4_row;      // LMAT_K4_ROW=1: tables of up to 16 taxids are decided by k4_row_kernel instead of on the classify wave (measured slower)
     int k4_chain;    // bit 0, cleared by LMAT_K4_CHAIN=0: no closed form for reads of one lineage (kernels.hip k4_wave_chain), the general code decides them;
                      // bit 1, cleared by LMAT_K4_PATH=0: none for reads of one dominant lineage (k4_wave_path);
-                     // bit 2, cleared by LMAT_K4_TIE=0: none for reads with tied ids at the top (k4_wave_tie).  (One field: the kernels' argument layout stays.)
+                     // bit 2, cleared by LMAT_K4_TIE=0: none for reads with tied ids at the top (k4_wave_tie);
+                     // bit 3, cleared by LMAT_CLOSURE_STRIDE=0: no closure walk at a fixed stride (classify_one); bit 4, set by LMAT_CLOSURE_STRIDE=2: the
+                     // generic kernel counts the reads that walk so (kCurStrideTaken).  (One field: the kernels' argument layout stays.)
     int k4_static;   // set by the launchers (kernels.hip k4_static_of): what the choice of decision path asks of the launch, not of the read
 };
 
