@@ -624,6 +624,66 @@ int lmat_cov_run(lmat_cov* c, lmat_cov_stats* out);
 int lmat_cov_summary(lmat_cov* c, int k_index, uint32_t* groups, uint64_t* distinct, uint64_t* total, uint64_t cap, uint64_t* n);
 int lmat_cov_histogram(lmat_cov* c, int k_index, uint32_t group, uint64_t* multiplicity, uint64_t* n_kmers, uint64_t cap, uint64_t* n);
 
+/* ---- reads pulled by called taxon (bin/pull_reads.pl behind bin/pull_reads_mc.sh; lmat_amd/csrc/bins.hip) ----
+ * Selects, on the device, the reads of a classified batch that belong to GROUPS of taxids and hands back, per group, their
+ * indices, the offsets of their text and (on request) the text itself, decoded from the packed records: only the pulled reads
+ * leave the GPU, and a run that did not echo its reads (-a), or whose reads have no host text at all, can still be pulled from.
+ *   the rule   pull_reads.pl:76-100 on the fields of a record exactly as the .out writer prints them:
+ *                status        tid                 score         third (the script's valid_kmers)   type
+ *                CALL, PHIX    call_tid (none: -1) call_score    cand_kmer_cnt                     the match type word
+ *                NODBHITS      read_len (sic)      k (sic)       valid_kmers                       NoDbHits
+ *                SHORT_LEN     read_len            k             -1                                ReadTooShort
+ *                SHORT_VALID   valid_kmers         -j min_kmer   -1                                ReadTooShort
+ *              1. tid is an id of a group, score >= thresh, third >= min_kmer: that group (an id listed by two groups belongs
+ *                 to the later one);  2. a LOWSCORE group exists, score < its score, third >= min_kmer: that group;  3. type
+ *                 NoDbHits, third >= min_kmer, a NODBHITS group exists: that group;  4. (ReadTooShort: the script selects
+ *                 nothing).  LMAT_ST_SILENT records are never selected by 1-3.  So a NoDbHits read of 202 bases is pulled by a
+ *                 group that lists 202, and NoDbHits reads reach LowScore first when its score is above k -- as upstream.
+ *              The score compares are made on the float the device holds; the script compares the 6-digit text.
+ *   flags      LMAT_BIN_SUBTREE  the group's ids stand for their clades in ctx's tree: exact ids first (of any group), then
+ *                                the nearest ancestor that a SUBTREE group owns.  Needs a loaded taxonomy (else LMAT_E_STATE);
+ *                                an id the tree does not hold stays an exact id.
+ *              LMAT_BIN_REST     the group takes every read no branch selected, SILENT ones included (depletion runs)
+ *              LMAT_BIN_LOWSCORE the LowScore group, with low_score;  LMAT_BIN_NODBHITS  the group branch 3 selects into
+ *              Of several groups with REST, LOWSCORE or NODBHITS the last one counts.  A group may have no ids and no flags.
+ *   groups     at most 65534 (LMAT_E_CAPACITY); a group is known by its position in the array (file: by its line among the
+ *              lines that make a group).  lmat_bins_set_from_file reads the script's grammar (pullfmt.hpp).
+ *   lmat_bins_run    on the result records the most recent launch left on the device, which must have been for exactly these
+ *              reads, first and count (lmat_classify, or lmat_classify_async* + lmat_sync); otherwise LMAT_E_STATE.  Blocking.
+ *   lmat_bins_counts reads and bases per group.   lmat_bins_fetch  of one group: read_idx[n] ascending, indices into `reads`;
+ *              base_off[n + 1] from 0; bases[base_off[n]] (ACGT, N for an invalid position) -- NULL, or a run without
+ *              want_bases (then LMAT_E_STATE for a non-NULL bases): none.  Any of the three may be NULL.
+ *   errors     a gene context: LMAT_E_ARG.  lmat_bins_run before lmat_bins_set, counts / fetch before a run: LMAT_E_STATE. */
+#define LMAT_BIN_SUBTREE  1u
+#define LMAT_BIN_REST     2u
+#define LMAT_BIN_LOWSCORE 4u
+#define LMAT_BIN_NODBHITS 8u
+#define LMAT_BIN_NONE 0xFFFFu   /* the group of a read no group takes */
+typedef struct lmat_bins lmat_bins;
+typedef struct {
+    const uint32_t* ids; uint32_t n_ids;   /* printed taxids (32-bit) */
+    uint32_t flags;                        /* LMAT_BIN_* */
+    float low_score;                       /* with LMAT_BIN_LOWSCORE */
+} lmat_bin_group;
+int lmat_bins_create(lmat_ctx* ctx, lmat_bins** out);
+void lmat_bins_destroy(lmat_bins* b);
+const char* lmat_bins_error(const lmat_bins* b);
+int lmat_bins_set(lmat_bins* b, const lmat_bin_group* groups, uint32_t n_groups, float thresh, int32_t min_kmer);
+int lmat_bins_set_from_file(lmat_bins* b, const char* idfile, float thresh, int32_t min_kmer);
+int lmat_bins_run(lmat_bins* b, const lmat_reads* reads, uint64_t first, uint64_t count, int want_bases);
+int lmat_bins_counts(lmat_bins* b, uint64_t* n_reads_per_group, uint64_t* n_bases_per_group);
+int lmat_bins_fetch(lmat_bins* b, uint32_t group, uint32_t* read_idx, uint64_t* base_off, uint8_t* bases);
+/* Test hook: uploads n records and runs the select kernel alone; group_out[i] = the group of record i or LMAT_BIN_NONE.
+ * k and -j min_kmer are the context's. */
+int lmat_debug_bins_select(lmat_bins* b, const lmat_read_result* host_results, uint64_t n, uint16_t* group_out);
+/* The streamed boundary with bins (NULL clears; applies to submits made afterwards; the slots' buffers are allocated here):
+ * select and partition run behind a slot's classify launches, ahead of its result copy -- also when the slot grows and the
+ * batch runs again -- and lmat_stream_next_bins gives, for the batch lmat_stream_next handed out, group_off[n_groups + 1] and
+ * read_idx[group_off[n_groups]] (indices into the batch, ascending per group), in pinned memory valid until the release.  No
+ * bases: the submitter holds the text.  A batch submitted without bins: LMAT_E_STATE. */
+int lmat_stream_set_bins(lmat_stream* st, lmat_bins* b);
+int lmat_stream_next_bins(lmat_stream* st, const uint64_t** group_off, const uint32_t** read_idx);
+
 /* ---- test hook: the decision step on given candidate tables ---------------------------------
  * Runs the decision kernels' own code -- std::sort(TCmp) (src/read_label.cpp:475-485, 892-893) and findReadLabelVer2
  * (:284-419) -- on n candidate tables given from outside instead of computed from reads: table i = the (32-bit taxid,

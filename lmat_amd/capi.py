@@ -226,6 +226,17 @@ def load_library(path: str | None = None):
         "lmat_stream_submit_pairs": (i32, [vp, u64, u64]),
         "lmat_stream_submit_pairs_from": (i32, [vp, vp, vp, vp, vp, u64, u64]),
         "lmat_image_check": (i32, [cp, vp, u64]),
+        "lmat_bins_create": (i32, [vp, P(vp)]),
+        "lmat_bins_destroy": (None, [vp]),
+        "lmat_bins_error": (cp, [vp]),
+        "lmat_bins_set": (i32, [vp, vp, u32, C.c_float, i32]),
+        "lmat_bins_set_from_file": (i32, [vp, cp, C.c_float, i32]),
+        "lmat_bins_run": (i32, [vp, vp, u64, u64, i32]),
+        "lmat_bins_counts": (i32, [vp, vp, vp]),
+        "lmat_bins_fetch": (i32, [vp, u32, vp, vp, vp]),
+        "lmat_debug_bins_select": (i32, [vp, vp, u64, vp]),
+        "lmat_stream_set_bins": (i32, [vp, vp]),
+        "lmat_stream_next_bins": (i32, [vp, P(vp), P(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -258,7 +269,9 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_export_taxid_counts", "lmat_export_set_filter", "lmat_export_filter_stats", "lmat_db_from_export", "lmat_build_add_db", "lmat_table_unaddress",
             "lmat_genebuild_create", "lmat_genedb_build_from_genes",
             "lmat_debug_stream_stats", "lmat_debug_reads_words",
-            "lmat_reads_upload_pairs", "lmat_stream_submit_pairs", "lmat_stream_submit_pairs_from", "lmat_image_check"]
+            "lmat_reads_upload_pairs", "lmat_stream_submit_pairs", "lmat_stream_submit_pairs_from", "lmat_image_check",
+            "lmat_bins_create", "lmat_bins_destroy", "lmat_bins_error", "lmat_bins_set", "lmat_bins_set_from_file", "lmat_bins_run", "lmat_bins_counts",
+            "lmat_bins_fetch", "lmat_debug_bins_select", "lmat_stream_set_bins", "lmat_stream_next_bins"]
 
 
 def image_check(path):
@@ -378,6 +391,29 @@ class Stream:
         eng._chk(self.lib.lmat_stream_create(eng.ctx, self.max_reads, self.max_bases, cands_per_read, n_slots, C.byref(h)))
         self.h = h
         self.in_flight = 0
+        self.bins = None
+        self._bins_used = False
+        self._ng = []   # per batch in flight: the group count of the bins it was submitted under
+
+    def set_bins(self, bins):
+        """Batches submitted from now on are partitioned by the groups of `bins` (a Bins of the same engine; None clears): next()
+        then returns their index lists as a fourth element."""
+        self.eng._chk(self.lib.lmat_stream_set_bins(self.h, bins.h if bins is not None else None))
+        self.bins = bins
+        self._bins_used = self._bins_used or bins is not None
+
+    def _lists(self):
+        """Of the batch next() holds: [read indices (into the batch, ascending) per group], or None for a batch submitted without bins."""
+        pg, pi = C.c_void_p(), C.c_void_p()
+        rc = self.lib.lmat_stream_next_bins(self.h, C.byref(pg), C.byref(pi))
+        if rc == -7:   # LMAT_E_STATE
+            return None
+        self.eng._chk(rc)
+        ng = self._ng[0]
+        goff = np.ctypeslib.as_array(C.cast(pg, C.POINTER(C.c_uint64)), shape=(ng + 1,)).copy()
+        total = int(goff[-1])
+        idx = np.ctypeslib.as_array(C.cast(pi, C.POINTER(C.c_uint32)), shape=(max(total, 1),))[:total].copy()
+        return [idx[int(goff[g]):int(goff[g + 1])] for g in range(ng)]
 
     def submit(self, blob, off, tag=0):
         """blob: uint8 ASCII bases, off: uint64[n + 1]; copied into the slot's pinned buffers, then queued."""
@@ -389,6 +425,7 @@ class Stream:
         C.memmove(po, off.ctypes.data, (n + 1) * 8)
         self.eng._chk(self.lib.lmat_stream_submit(self.h, n, tag))
         self.in_flight += 1
+        self._ng.append(self.bins.n_groups if self.bins is not None else None)
 
     def submit_pinned(self, bases_ptr, off, n, tag=0):
         """bases_ptr: address of the caller's own pinned buffer (host_alloc); off: uint64[n + 1] numpy array.  No copy."""
@@ -396,6 +433,7 @@ class Stream:
         self.eng._chk(self.lib.lmat_stream_acquire(self.h, C.byref(pb), C.byref(po)))
         self.eng._chk(self.lib.lmat_stream_submit_from(self.h, bases_ptr, off.ctypes.data, n, tag))
         self.in_flight += 1
+        self._ng.append(self.bins.n_groups if self.bins is not None else None)
 
     def submit_pairs(self, blob, off, tag=0):
         """Paired-end: blob/off hold 2n reads, mates 1 and 2 in turn (off: uint64[2n + 1]); copied into the slot, joined on the
@@ -412,6 +450,7 @@ class Stream:
                 C.memmove(pb, blob.ctypes.data, int(off[-1]))
         self.eng._chk(self.lib.lmat_stream_submit_pairs(self.h, n2 // 2, tag))
         self.in_flight += 1
+        self._ng.append(self.bins.n_groups if self.bins is not None else None)
 
     def submit_pairs_pinned(self, ptr1, off1, ptr2, off2, n, tag=0):
         """Paired-end: mates 1 are off1[0..n] in the caller's pinned buffer at ptr1, mates 2 off2[0..n] at ptr2.  No host copy."""
@@ -419,6 +458,7 @@ class Stream:
         self.eng._chk(self.lib.lmat_stream_acquire(self.h, C.byref(pb), C.byref(po)))
         self.eng._chk(self.lib.lmat_stream_submit_pairs_from(self.h, ptr1, off1.ctypes.data, ptr2, off2.ctypes.data, n, tag))
         self.in_flight += 1
+        self._ng.append(self.bins.n_groups if self.bins is not None else None)
 
     def next_nocopy(self):
         """Waits for the oldest batch and releases it at once -> (n_reads, n_cands, tag), or None."""
@@ -430,6 +470,8 @@ class Stream:
         self.eng._chk(rc)
         self.eng._chk(self.lib.lmat_stream_release(self.h))
         self.in_flight -= 1
+        if self._ng:   # (a batch submitted through the library directly has no entry)
+            self._ng.pop(0)
         return int(n.value), int(nc.value), int(tag.value)
 
     def next(self):
@@ -444,8 +486,13 @@ class Stream:
         cands = None
         if pc.value and nc.value:
             cands = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_uint8)), shape=(nc.value * CAND_DTYPE.itemsize,)).view(CAND_DTYPE).copy()
+        lists = self._lists() if self._bins_used else None
         self.eng._chk(self.lib.lmat_stream_release(self.h))
         self.in_flight -= 1
+        if self._ng:   # (a batch submitted through the library directly has no entry)
+            self._ng.pop(0)
+        if self._bins_used:
+            return res, cands, int(tag.value), lists
         return res, cands, int(tag.value)
 
     STATS = ("uniform", "general", "threaded", "class_lists", "grow_reruns", "cand_cap")
@@ -460,10 +507,89 @@ class Stream:
         """Releases the oldest batch after next() has raised its error: the batches behind it come next."""
         self.eng._chk(self.lib.lmat_stream_release(self.h))
         self.in_flight -= 1
+        if self._ng:   # (a batch submitted through the library directly has no entry)
+            self._ng.pop(0)
 
     def close(self):
         if self.h:
             self.lib.lmat_stream_destroy(self.h)
+            self.h = None
+
+
+BIN_SUBTREE, BIN_REST, BIN_LOWSCORE, BIN_NODBHITS, BIN_NONE = 1, 2, 4, 8, 0xFFFF   # LMAT_BIN_*
+
+
+class BinGroup(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("n_ids", C.c_uint32), ("flags", C.c_uint32), ("low_score", C.c_float)]
+
+
+class Bins:
+    """lmat_bins: the reads of a classified batch pulled by called taxon on the GPU (upstream's bin/pull_reads.pl).
+    A group is (ids, flags) or (ids, flags, low_score); flags are BIN_*."""
+
+    def __init__(self, eng):
+        self.eng, self.lib = eng, eng.lib
+        h = C.c_void_p()
+        eng._chk(self.lib.lmat_bins_create(eng.ctx, C.byref(h)))
+        self.h = h
+        self.n_groups = 0
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise LmatError(rc, self.lib.lmat_bins_error(self.h).decode(errors="replace"))
+
+    def set(self, groups, thresh, min_kmer):
+        keep = []
+        arr = (BinGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            ids = np.ascontiguousarray(np.asarray(g[0], dtype=np.uint32))
+            keep.append(ids)
+            arr[i].ids = ids.ctypes.data if ids.size else None
+            arr[i].n_ids = ids.size
+            arr[i].flags = int(g[1]) if len(g) > 1 else 0
+            arr[i].low_score = float(g[2]) if len(g) > 2 else 0.0
+        self._chk(self.lib.lmat_bins_set(self.h, C.cast(arr, C.c_void_p), len(groups), float(thresh), int(min_kmer)))
+        self.n_groups = len(groups)
+
+    def set_file(self, idfile, thresh, min_kmer):
+        """The script's id file: every non-blank line makes a group, in file order -> the first token of each (its file's suffix)."""
+        self._chk(self.lib.lmat_bins_set_from_file(self.h, os.fsencode(idfile), float(thresh), int(min_kmer)))
+        names = [l.split()[0] for l in open(idfile) if l.split()]
+        self.n_groups = len(names)
+        return names
+
+    def run(self, reads, first=0, count=None, want_bases=True):
+        """On the records of the most recent classify launch, which must have been for exactly reads[first : first + count]
+        -> {group: (read indices into `reads` uint32[n] ascending, offsets uint64[n + 1], bases uint8 or None)}"""
+        n = len(reads) - first if count is None else count
+        self._chk(self.lib.lmat_bins_run(self.h, reads.h, first, n, 1 if want_bases else 0))
+        nr, nb = self.counts()
+        out = {}
+        for g in range(self.n_groups):
+            idx = np.zeros(max(int(nr[g]), 1), dtype=np.uint32)
+            off = np.zeros(int(nr[g]) + 1, dtype=np.uint64)
+            bases = np.zeros(max(int(nb[g]), 1), dtype=np.uint8) if want_bases else None
+            self._chk(self.lib.lmat_bins_fetch(self.h, g, _ptr(idx), _ptr(off), _ptr(bases)))
+            out[g] = (idx[:int(nr[g])], off, bases[:int(nb[g])] if want_bases else None)
+        return out
+
+    def counts(self):
+        """-> (reads per group uint64[n_groups], bases per group uint64[n_groups]) of the last run"""
+        nr = np.zeros(max(self.n_groups, 1), dtype=np.uint64)
+        nb = np.zeros(max(self.n_groups, 1), dtype=np.uint64)
+        self._chk(self.lib.lmat_bins_counts(self.h, _ptr(nr), _ptr(nb)))
+        return nr[:self.n_groups], nb[:self.n_groups]
+
+    def select_debug(self, results):
+        """The select kernel alone on given records (READ_RESULT_DTYPE) -> group per record, uint16 (BIN_NONE: none)"""
+        res = np.ascontiguousarray(results, dtype=READ_RESULT_DTYPE)
+        out = np.full(max(res.size, 1), BIN_NONE, dtype=np.uint16)
+        self._chk(self.lib.lmat_debug_bins_select(self.h, _ptr(res), res.size, _ptr(out)))
+        return out[:res.size]
+
+    def close(self):
+        if self.h:
+            self.lib.lmat_bins_destroy(self.h)
             self.h = None
 
 

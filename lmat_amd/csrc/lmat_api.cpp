@@ -11,6 +11,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include "kernels.hpp"
+#include "bins.hpp"
 #include "outfmt.hpp"
 
 using namespace lmat;
@@ -1473,6 +1474,7 @@ uint64_t lmat_reads_device_bytes(const lmat_reads* r) { return r ? r->n_words * 
 void lmat_reads_free(lmat_ctx* c, lmat_reads* r) {
     if (!r) return;
     if (c) hipSetDevice(c->device);
+    if (c && c->last_reads == r) c->last_reads = nullptr;
     if (r->words) hipFree(r->words);
     if (r->rec_off) hipFree(r->rec_off);
     for (int j = 0; j < kNCls; ++j) if (r->cls_dev[j]) hipFree(r->cls_dev[j]);
@@ -1725,6 +1727,14 @@ static int finish_launch(lmat_ctx* c, BatchSet& s, LaunchEvents& ev, hipStream_t
     return LMAT_OK;
 }
 
+// what lmat_bins_run may select on: the records this launch leaves in the set's own result buffer
+static void note_launch(lmat_ctx* c, const lmat_reads* reads, uint64_t first, uint64_t count) {
+    if (c->out_results || c->rand_launch) return;
+    c->last_reads = reads;
+    c->last_first = first;
+    c->last_count = count;
+}
+
 // pipelined: the launch takes the other set of per-batch buffers and returns with its decision kernels still running on the
 // side streams (beside whatever the caller queues next on the context's stream); the set's `done` event marks their end.
 // Otherwise the context's stream waits for them, as every caller that reads results right away needs.
@@ -1737,6 +1747,7 @@ static int run_classify(lmat_ctx* c, const lmat_reads* reads, uint64_t first, ui
     if ((int)reads->max_len > max_read_len_of(c)) return err_read_too_long(c);
     if (c->dev.wide && !c->dev.cpt.nb) return set_err(c, LMAT_E_ARG, "a wide taxonomy needs the compact table layout (k >= 10)");
     hipSetDevice(c->device);
+    c->last_reads = nullptr;
     int rc = prepare_set(c, count, want_cands, cand_cap, pipelined);
     if (rc) return rc;
     BatchSet& s = c->set();
@@ -1760,7 +1771,9 @@ static int run_classify(lmat_ctx* c, const lmat_reads* reads, uint64_t first, ui
         for (const Tier& t : chain)
             if (t.on && !launch_tier(s, a, t)) return err_read_too_long(c);
         if (timed) { HIPCHK(c, hipEventRecord(ev.e[1], c->stream)); HIPCHK(c, hipEventRecord(ev.e[2], c->stream)); }
-        return finish_launch(c, s, ev, c->stream, false);
+        rc = finish_launch(c, s, ev, c->stream, false);
+        if (!rc) note_launch(c, reads, first, count);
+        return rc;
     }
     if ((rc = build_class_lists(c, const_cast<lmat_reads*>(reads)))) return rc;
     ClassSpan spans[kNCls];
@@ -1817,7 +1830,9 @@ static int run_classify(lmat_ctx* c, const lmat_reads* reads, uint64_t first, ui
     // the tiers join on the context's stream, or, when the next batch is to run beside them, on the second stream
     hipStream_t js = k4 && pipelined ? c->stream2 : c->stream;
     if (k4) launch_k4_end(a, js, c->stream2, c->stream3, small, c->ev_join, c->ev_join3, c->ev_join_small, s.done);
-    return finish_launch(c, s, ev, js, k4);
+    rc = finish_launch(c, s, ev, js, k4);
+    if (!rc) note_launch(c, reads, first, count);
+    return rc;
 }
 
 // Device error flags -> the API's code and message (the most specific message wins); LMAT_OK for none.
@@ -2281,8 +2296,11 @@ struct lmat_stream {
         uint64_t n = 0, tag = 0;
         int state = 0;               // 0 free, 1 acquired, 2 in flight, 3 handed to the caller
         bool failed = false;         // in flight, and lmat_stream_next has reported this batch's error
+        lmat::BinsPart bp;           // index lists of the batch (bins.hip), allocated by lmat_stream_set_bins
+        lmat_bins* bins = nullptr;   // the bins the batch was submitted under (a grow re-run partitions by the same)
     };
     lmat_ctx* c = nullptr;
+    lmat_bins* bins = nullptr;       // submits partition their batch by these groups
     std::vector<Slot> slots;
     uint64_t max_reads = 0, max_bases = 0;
     uint32_t cands_per_read = 0;
@@ -2389,6 +2407,13 @@ static int stream_launch(lmat_stream* st, lmat_stream::Slot& sl, bool to_scratch
     const int rc = run_classify(c, &sl.reads, 0, sl.n, sl.cand_cap != 0, sl.cand_cap, false, pipeline_on());
     c->out_results = nullptr; c->out_cands = nullptr; c->out_counts = nullptr; c->batch_err = false;
     if (rc) return rc;
+    // bins (lmat_stream_set_bins): select + partition on the slot's records, behind the batch's kernels and ahead of the copies below;
+    // a grow re-run comes through here again, so the lists are those of the final records
+    sl.bp.valid = false;
+    if (sl.bins) {
+        const int brc = bins_part_queue(sl.bins, sl.bp, sl.d_results, sl.n, 0, c->join_stream);
+        if (brc) return set_err(c, brc, lmat_bins_error(sl.bins));
+    }
     // The counters are copied out on the stream the batch's kernels joined on, and the set's `done` event is recorded again
     // behind that copy: the next launch that takes this set of buffers clears the counters, and must not overtake it.
     // The results ride the context's second stream (idle once the decision kernels have joined; with LMAT_PIPELINE it is
@@ -2542,6 +2567,12 @@ static int stream_submit(lmat_stream* st, uint64_t n, uint64_t tag, const uint8_
         sl.state = 0;
         return err_read_too_long(c);
     }
+    sl.bp.valid = false;
+    sl.bins = st->bins;
+    if (!n && st->bins) {   // an empty batch: empty lists
+        memset(sl.bp.h_goff.p, 0, ((size_t)bins_group_count(st->bins) + 1) * 8);
+        sl.bp.valid = true;
+    }
     if (n) {
         if (PAIRS == 2) {
             if (sum1) HIPCHK(c, hipMemcpyAsync(sl.d_bases, ext_bases, sum1, hipMemcpyHostToDevice, st->s_h2d));
@@ -2675,6 +2706,30 @@ int lmat_stream_release(lmat_stream* st) {
     sl.state = 0;
     sl.failed = false;
     ++st->tail;
+    return LMAT_OK;
+}
+
+int lmat_stream_set_bins(lmat_stream* st, lmat_bins* b) {
+    if (!st) return LMAT_E_ARG;
+    lmat_ctx* c = st->c;
+    if (!b) { st->bins = nullptr; return LMAT_OK; }
+    if (bins_ctx(b) != c) return set_err(c, LMAT_E_ARG, "the bins belong to another context");
+    hipSetDevice(c->device);
+    for (auto& sl : st->slots) {
+        const int rc = bins_part_alloc(b, sl.bp, st->max_reads, true);
+        if (rc) return set_err(c, rc, lmat_bins_error(b));
+    }
+    st->bins = b;
+    return LMAT_OK;
+}
+
+int lmat_stream_next_bins(lmat_stream* st, const uint64_t** group_off, const uint32_t** read_idx) {
+    if (!st) return LMAT_E_ARG;
+    lmat_stream::Slot& sl = st->slots[st->tail % st->slots.size()];
+    if (sl.state != 3) return set_err(st->c, LMAT_E_ARG, "no batch is checked out");
+    if (!sl.bp.valid) return set_err(st->c, LMAT_E_STATE, "the batch was submitted without bins");
+    if (group_off) *group_off = sl.bp.h_goff.as<uint64_t>();
+    if (read_idx) *read_idx = sl.bp.h_idx.as<uint32_t>();
     return LMAT_OK;
 }
 

@@ -199,6 +199,10 @@ struct lmat_ctx {
     BatchSet sets[2];
     int cur_set = 0;
     BatchSet& set() { return sets[cur_set]; }   // the set of the most recent launch
+    // what that launch classified into the set's own result buffer (bins.hip selects on those records); last_reads null: nothing it
+    // could select on (no launch yet, a launch of the streamed boundary or of rand_read_label, or the reads were freed since)
+    const lmat_reads* last_reads = nullptr;
+    uint64_t last_first = 0, last_count = 0;
     lmat_dev::DevBuf gscratch;     // tables of the global-memory class, allocated on first use
     hipStream_t stream2 = nullptr;  // the scratch K4 kernel runs beside the LDS one
     hipStream_t stream3 = nullptr;  // ... and the LDS kernel of the largest tables beside both

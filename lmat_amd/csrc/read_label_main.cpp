@@ -45,6 +45,7 @@
 #include "../../include/lmat_hip.h"
 #include "fastx.hpp"
 #include "outfmt.hpp"
+#include "pullfmt.hpp"
 #include "rollups.hpp"
 
 #define LMAT_VERSION "1.2.4_2018a"
@@ -65,6 +66,9 @@ static void usage(const char* exe) {
     std::cout << "     mate 1, an N, mate 2, under mate 1's header (what merge_fastq_reads_with_N_separator.pl writes to disk); both" << std::endl;
     std::cout << "     files are read with the same -q setting; mate names are not compared (upstream's check compares mate 1's" << std::endl;
     std::cout << "     name with itself); files that hold different numbers of reads are an error; not with -i -" << std::endl;
+    std::cout << "[-B <id file> [-S <min score, default 1>] [-K <min k-mers, default 15>] [-O <dir, default: that of -o>]] pull reads by" << std::endl;
+    std::cout << "     called taxon while classifying: for every <o><N>.out the files bin/pull_reads.pl writes for it under that id file" << std::endl;
+    std::cout << "     (<dir>/<out name>.<id file name>.pulled.<first token of the line>), selected on the GPU; works with -a" << std::endl;
 }
 
 static bool is_list_file(const std::string& fn) {
@@ -244,6 +248,7 @@ struct Work {
     std::unique_ptr<lmat_cand[]> cands;  // uninitialised on purpose: zero-filling 64 candidates per read cost more than the GPU work
     size_t ncand = 0;
     std::vector<std::string> text;       // per output shard, once formatted
+    std::vector<uint16_t> grp;           // -B: the group of every read (LMAT_BIN_NONE: not pulled)
 };
 class WorkQueue {
     std::mutex m;
@@ -291,7 +296,10 @@ int main(int argc, char* argv[]) {
     bool fastq = false, prn_read = true;
     int permissive = 0, max_count = 0;
     std::string rank_table_file;
-    while ((c = getopt(argc, argv, "u:ahn:j:b:ye:w:pk:c:v:k:i:d:l:t:r:sm:o:x:f:g:z:qVH2:")) != -1) {
+    std::string pull_idfile, pull_odir;   // -B / -O; the defaults of -S and -K are those of bin/pull_reads_mc.sh:4-6
+    float pull_score = 1.0f;
+    int pull_kmers = 15;
+    while ((c = getopt(argc, argv, "u:ahn:j:b:ye:w:pk:c:v:k:i:d:l:t:r:sm:o:x:f:g:z:qVH2:B:S:K:O:")) != -1) {
         switch (c) {
             case 'h': prm.screen_phix = 0; break;
             case 'r': plasmid_file = optarg; break;
@@ -318,6 +326,10 @@ int main(int argc, char* argv[]) {
             case 'g': max_count = atoi(optarg); break;
             case 'i': query_fn = optarg; break;
             case '2': query2_fn = optarg; break;
+            case 'B': pull_idfile = optarg; break;
+            case 'S': pull_score = (float)atof(optarg); break;
+            case 'K': pull_kmers = atoi(optarg); break;
+            case 'O': pull_odir = optarg; break;
             case 'd': kmer_db_fn = optarg; break;
             case 'o': ofbase = optarg; break;
             case 'V': std::cout << "LMAT version " << LMAT_VERSION << std::endl; exit(0);
@@ -341,6 +353,13 @@ int main(int argc, char* argv[]) {
         return -1;
     }
     const bool paired = !query2_fn.empty();
+    const bool pulling = !pull_idfile.empty();
+    std::vector<PullGroup> pull_groups;
+    if (pulling) {
+        std::string perr;
+        if (!parse_pull_idfile(pull_idfile.c_str(), pull_groups, perr)) { std::cerr << "ERROR! -B: " << perr << std::endl; return -1; }
+        if (pull_odir.empty()) { const size_t sl = ofbase.rfind('/'); pull_odir = sl == std::string::npos ? "." : ofbase.substr(0, sl ? sl : 1); }
+    }
     // no -f: a database of 32-bit taxids (upstream's TID_SIZE=32 build); storage codes come from the tree
     prm.min_score = min_score;
     prm.min_kmer = min_kmer;
@@ -361,8 +380,10 @@ int main(int argc, char* argv[]) {
     const int n_gpu = (int)devices.size();
     std::vector<lmat_ctx*> ctxs(n_gpu, nullptr);
     std::vector<lmat_stream*>* rings_p = nullptr;
+    std::vector<lmat_bins*> bins(n_gpu, nullptr);   // -B: one per context, set on its ring
     auto destroy_all = [&]() {
         if (rings_p) for (lmat_stream*& r : *rings_p) { if (r) lmat_stream_destroy(r); r = nullptr; }
+        for (lmat_bins*& b : bins) { if (b) lmat_bins_destroy(b); b = nullptr; }
         for (lmat_ctx*& x : ctxs) { if (x) lmat_ctx_destroy(x); x = nullptr; }
     };
     for (int g = 0; g < n_gpu; ++g)
@@ -463,6 +484,11 @@ int main(int argc, char* argv[]) {
                         if (*img && lmat_db_save_image(x, img) != LMAT_OK) return bad("device image");
                 if (g == 0) { sig.ok = true; sig.p->set_value(true); sig.p = nullptr; }
                 if (lmat_stream_create(x, kBatch, kBatchBases, cands_per_read, kSlots, &rings[g]) != LMAT_OK) return bad("batch ring");
+                if (pulling) {
+                    if (lmat_bins_create(x, &bins[g]) != LMAT_OK) return bad("-B");
+                    if (lmat_bins_set_from_file(bins[g], pull_idfile.c_str(), pull_score, pull_kmers) != LMAT_OK) { setup_err[g] = std::string("-B: ") + lmat_bins_error(bins[g]); return; }
+                    if (lmat_stream_set_bins(rings[g], bins[g]) != LMAT_OK) return bad("-B");
+                }
             });
         for (auto& x : th) x.join();
     }
@@ -505,6 +531,14 @@ int main(int argc, char* argv[]) {
         std::ostringstream nm;
         nm << ofbase << t << ".out";
         shard[t].fd = open(nm.str().c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    }
+    // -B: the pulled files of every shard, written by the sequencer below in input order (uid counts per .out file)
+    std::vector<PullWriter> pullers(pulling ? n_threads : 0);
+    for (int t = 0; t < (int)pullers.size(); ++t) {
+        std::ostringstream nm;
+        nm << ofbase << t << ".out";
+        std::string perr;
+        if (!pullers[t].open(pull_odir, nm.str(), pull_idfile, pull_groups, perr)) { std::cerr << "ERROR! -B: " << perr << std::endl; destroy_all(); return -1; }
     }
     std::vector<std::thread> shard_writers;
     for (int t = 0; t < n_threads; ++t)
@@ -833,6 +867,27 @@ int main(int argc, char* argv[]) {
             const std::vector<lmat_read_result>& res = w->res;
             const size_t n = w->b.n();
             for (int t = 0; t < n_threads; ++t) shard_push(t, std::move(w->text[t]));
+            if (pulling && n) {   // the reads the GPU selected, with the host's own text (shard t holds the block format_batch gave it)
+                const Batch& b = w->b;
+                const size_t per = (n + n_threads - 1) / n_threads;
+                std::string joined;
+                for (int t = 0; t < n_threads; ++t) {
+                    const size_t lo = std::min(n, t * per), hi = std::min(n, lo + per);
+                    for (size_t i = lo; i < hi; ++i) {
+                        if (w->grp[i] == LMAT_BIN_NONE) continue;
+                        const char* rd = (const char*)b.bases + b.off[i];
+                        size_t rl = b.off[i + 1] - b.off[i];
+                        if (b.paired()) {
+                            joined.assign(rd, rl);
+                            joined += 'N';
+                            joined.append((const char*)b.bases2() + b.off2[i], b.off2[i + 1] - b.off2[i]);
+                            rd = joined.data();
+                            rl = joined.size();
+                        }
+                        pullers[t].put(w->grp[i], b.hdr_blob.data() + b.hoff[i], b.hoff[i + 1] - b.hoff[i], rd, rl, pull_fields(prm, k_size, res[i]));
+                    }
+                }
+            }
             auto tp4 = now();
             t_write_seq += secs(tp3, tp4);
             // tallies in read order (proc_line :1241-1276), float sums like a -t 1 run.  One thread sees every record, so the
@@ -891,6 +946,13 @@ int main(int argc, char* argv[]) {
                 w.cands = std::move(grown);
                 w.ncand = c0 + nc;
                 for (uint64_t i = 0; i < n; ++i) { w.res[at + i] = res[i]; w.res[at + i].cand_off += (uint32_t)c0; }
+                if (pulling) {
+                    const uint64_t* goff = nullptr;
+                    const uint32_t* idx = nullptr;
+                    if (lmat_stream_next_bins(st, &goff, &idx) != LMAT_OK) return false;
+                    for (size_t gi = 0; gi < pull_groups.size(); ++gi)
+                        for (uint64_t j = goff[gi]; j < goff[gi + 1]; ++j) w.grp[at + idx[j]] = (uint16_t)gi;
+                }
                 lmat_stream_release(st);
                 return true;
             };
@@ -906,6 +968,7 @@ int main(int argc, char* argv[]) {
                 if (w) {
                     const size_t n = w->b.n();
                     w->res.resize(n);
+                    if (pulling) w->grp.assign(n, (uint16_t)LMAT_BIN_NONE);
                     if (n == 0) { classified.push(std::move(w)); continue; }  // an empty piece keeps its place in the order
                     uint8_t* hb = nullptr;
                     uint64_t* ho = nullptr;
@@ -946,6 +1009,11 @@ int main(int argc, char* argv[]) {
     writer.join();
     for (auto& so : shard) { std::lock_guard<std::mutex> l(so.m); so.closed = true; so.cv.notify_all(); }
     for (auto& x : shard_writers) x.join();
+    for (auto& pw : pullers)
+        if (!pw.close()) {
+            std::lock_guard<std::mutex> l(fail_m);
+            if (!failed.exchange(true)) fail_msg = "cannot write a pulled file under " + pull_odir;
+        }
     for (auto& so : shard) {
         t_write = std::max(t_write, so.busy);
         if (so.fd < 0 || so.bad || close(so.fd) != 0) {
