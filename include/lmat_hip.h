@@ -195,6 +195,8 @@ int lmat_debug_div_check(lmat_ctx* ctx, uint64_t* out4);
 int lmat_debug_variant_launches(lmat_ctx* ctx, uint64_t* out2);
 /* of the launches counted in out2[1]: those that ran as the fixed-geometry variant (every read of 148 .. 151 bases at k = 20) */
 int lmat_debug_uniform_launches(lmat_ctx* ctx, uint64_t* out);
+/* the grid of the last launch counted in out2 (0: none yet): its wave b classified reads b, b + grid, b + 2 grid, ... of the launch */
+int lmat_debug_classify_grid(lmat_ctx* ctx, uint32_t* out);
 
 /* Test hook for the synthetic database: what it must hold for the window of `species` (0-based) that starts at base `pos` of the
  * species ancestor -- the canonical k-mer and its taxid list (the strains that carry the window unmutated; with two or more

@@ -184,6 +184,7 @@ def load_library(path: str | None = None):
         "lmat_debug_div_check": (i32, [vp, vp]),
         "lmat_debug_variant_launches": (i32, [vp, vp]),
         "lmat_debug_uniform_launches": (i32, [vp, vp]),
+        "lmat_debug_classify_grid": (i32, [vp, vp]),
         "lmat_synth_read_windows": (i32, [vp, vp, u32, u64, u64, vp, vp, vp, u32, u32, P(u32), P(u32)]),
         "lmat_table_address": (i32, [i32, u64, u64, P(u64), P(u32), P(u32)]),
         "lmat_format_out": (C.c_int64, [vp, vp, u64, vp, vp, vp, i32, u64, vp, u64]),
@@ -259,7 +260,7 @@ EXPORTED = ["lmat_device_count", "lmat_ctx_create", "lmat_ctx_destroy", "lmat_la
             "lmat_counts_reset", "lmat_counts_layout", "lmat_counts_device_ptr", "lmat_counts_get", "lmat_gather_bench",
             "lmat_table_address", "lmat_format_out", "lmat_stream_create", "lmat_stream_acquire", "lmat_stream_submit", "lmat_stream_submit_from", "lmat_host_alloc", "lmat_host_free",
             "lmat_stream_next", "lmat_stream_release", "lmat_stream_destroy", "lmat_counts_allreduce",
-            "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_debug_decide_chain", "lmat_debug_decide_shape", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check", "lmat_debug_variant_launches", "lmat_debug_uniform_launches",
+            "lmat_comm_unique_id", "lmat_comm_init", "lmat_comm_allreduce_counts", "lmat_comm_size", "lmat_comm_destroy", "lmat_db_clone", "lmat_debug_decide", "lmat_debug_decide_counts", "lmat_debug_decide_chain", "lmat_debug_decide_shape", "lmat_synth_window", "lmat_synth_read_windows", "lmat_debug_probe_stats", "lmat_debug_last_counters", "lmat_debug_div_check", "lmat_debug_variant_launches", "lmat_debug_uniform_launches", "lmat_debug_classify_grid",
             "lmat_build_create", "lmat_build_destroy", "lmat_build_error", "lmat_build_set_options", "lmat_build_add_fasta", "lmat_build_add_sequence",
             "lmat_build_run", "lmat_build_write_taxhisto", "lmat_build_fetch", "lmat_db_build_from_genomes",
             "lmat_build_add_taxhisto", "lmat_build_merge_stats", "lmat_build_taxid_counts",
@@ -1234,6 +1235,13 @@ class Engine:
         148 .. 151 bases at k = 20 (LMAT_UNIFORM)."""
         out = np.zeros(1, dtype=np.uint64)
         self._chk(self.lib.lmat_debug_uniform_launches(self.ctx, _ptr(out)))
+        return int(out[0])
+
+    def classify_grid(self):
+        """-> the grid of the last launch that variant_launches() counted (0: none yet): wave b of it classified reads b, b + grid,
+        b + 2 grid, ... of the launch."""
+        out = np.zeros(1, dtype=np.uint32)
+        self._chk(self.lib.lmat_debug_classify_grid(self.ctx, _ptr(out)))
         return int(out[0])
 
     def div_check(self):

@@ -58,6 +58,7 @@ void launch_k4_debug(const ClassifyArgs&, const uint32_t*, const float*, const u
 void launch_k4_debug_counts(const ClassifyArgs&, const uint32_t*, const uint32_t*, const uint64_t*, const uint32_t*, uint64_t, bool, hipStream_t, const uint32_t*, uint8_t*) {}
 void classify_variant_launches(int, uint64_t out[2]) { out[0] = out[1] = 0; }
 uint64_t classify_uniform_launches(int) { return 0; }
+uint32_t classify_last_grid(int) { return 0; }
 int classify_max_read_len(int k) { return 32768 + (k >= 1 && k <= 20 ? k : 20) - 1; }
 size_t classify_gmem_scratch_bytes() { return 1 << 20; }
 void launch_gather_bench(const uint64_t*, uint32_t, uint64_t, uint64_t, unsigned long long*, hipStream_t, int) {}

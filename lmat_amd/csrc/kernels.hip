@@ -34,6 +34,12 @@
 #ifndef LMAT_EVEN_K
 #define LMAT_EVEN_K 3         // (A/B builds: bit 0 off: the plain variants compare digests inside a run; bit 1 off: they carry the palindrome bit)
 #endif
+#ifndef LMAT_PREFETCH_ALWAYS
+#define LMAT_PREFETCH_ALWAYS 1   // (A/B builds: -DLMAT_PREFETCH_ALWAYS=0: the next record's load under `more`, the first record unsettled at the loop header)
+#endif
+#ifndef LMAT_TAIL_EARLY
+#define LMAT_TAIL_EARLY 1     // (A/B builds: -DLMAT_TAIL_EARLY=0: a read's tail entries are loaded in the c == 2 arm of pass 1, where they are consumed)
+#endif
 #ifndef LMAT_LDS_SHIFT
 #define LMAT_LDS_SHIFT 0   // (-DLMAT_LDS_SHIFT=1: the lane shifts of the minimizer window and the repeat filter through LDS instead of DPP.
                            //  Measured in round 4, same box: 24.57 against 24.29 ms per 8 M reads -- 60 vector instructions fewer per read,
@@ -2336,6 +2342,20 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         tail_flag = (uint32_t)__builtin_amdgcn_readfirstlane((lpr != 0 && P > 128u && P <= 128u + lpr && !(PLAIN ? 0u : A.nm.active)) ? 1 : 0);  // (a scalar, not a lane mask re-materialised from its conditions)
     }
     auto tail_mode = [&]() -> bool { return TAILOK && (UNI || tail_flag != 0); };
+    // TAIL_EARLY: the read's tail entries are asked for here, with nothing waiting on them, and consumed in the c == 2 arm of pass 1
+    // -- their trip to HBM (tail_kernel wrote them: they are in no cache) runs under the record's way to LDS and pass 1 of the two
+    // full chunks, beside the next record's, instead of standing exposed in front of cpt_finish.  Six registers live across pass 1,
+    // none across the probe phase: the generic <160,64,256> instantiations stay at their 64 (profiles/front_trips_static.txt).
+    constexpr bool TAIL_EARLY = TAILOK && LMAT_TAIL_EARLY;
+    u32x4 te = {0u, 0u, 0u, 0u};
+    uint64_t tu = 0;
+    auto tail_load = [&]() {
+        const uint32_t lpr = PLAIN ? 4u : A.tail_lpr;
+        const uint64_t ri = r - A.result_base;
+        if ((uint32_t)lane < lpr) te = ((const GAS u32x4*)A.tail16)[ri * lpr + lane];
+        if (lane < 3) tu = ((const GAS uint64_t*)A.tail_u)[ri * 4 + lane];
+    };
+    if constexpr (TAIL_EARLY) { if (tail_mode()) tail_load(); }
     // ---- packed record -> LDS (coalesced), zero tail so windows past the end are invalid
     const uint32_t nb = UNI ? 10u : (len + 15) / 16, nm = UNI ? 5u : (len + 31) / 32;
 #pragma unroll
@@ -2517,12 +2537,7 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         for (int c = 0; c < CH; ++c) {
             if (!UNI && (uint32_t)c * 64 >= len) break;
             if (TAILOK && c == 2 && tail_mode()) {  // looked up beforehand: k-mer, bucket, minimizer offset; the payload goes straight to its place
-                const uint32_t lpr = PLAIN ? 4u : A.tail_lpr;
-                const uint64_t ri = r - A.result_base;
-                u32x4 te = {0u, 0u, 0u, 0u};
-                uint64_t tu = 0;
-                if ((uint32_t)lane < lpr) te = ((const GAS u32x4*)A.tail16)[ri * lpr + lane];
-                if (lane < 3) tu = ((const GAS uint64_t*)A.tail_u)[ri * 4 + lane];
+                if constexpr (!TAIL_EARLY) tail_load();
                 kreg[c] = ((uint64_t)(te.y & 0xFFu) << 32) | te.x;
                 hreg[c] = te.z;
                 treg[c] = te.w & 0xC0000000u;
@@ -4454,7 +4469,8 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
     LAS unsigned char* xl = (LAS unsigned char*)(U > 2048 ? lds_smem : lds_smem + WL<U, T, E, INK4, CPT, WIDE>::OFF_XL);
     const int lane = threadIdx.x & 63;
     // Software pipeline over the reads of this wave: the record offset is fetched two reads ahead and the
-    // record words one read ahead, so a read never starts with a chain of dependent HBM round trips.
+    // record words one read ahead, so a read never starts with a chain of dependent HBM round trips (FRONT below: nor by waiting
+    // for the trip it has just started).
     // What the loop needs from the kernel arguments (read count, list and record pointers) is read again in every trip -- scalar
     // loads from the argument segment -- instead of being carried across classify_one, where every carried scalar is one more
     // value spilled to a lane of a vector register around the decision step (the kernel has 78 scalar registers).
@@ -4464,17 +4480,29 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
     uint32_t wcur[NW], wnext[NW];
     uint32_t nmacc[2] = {0, 0};
     uint64_t off1 = 0;
+    // FRONT (the 160-k-mer compact classes of up to 64 taxids): the prefetch is asked for on every trip, not under `more` -- past the
+    // launch's last read the index is clamped to that read, whose record (and offset) is loaded again and dropped -- and the first
+    // record is waited for before the loop.  Every path into the loop header and through it then has the same loads in flight and
+    // none that the read's first instructions consume: the first wait on vector memory in a read is the one its tail entries need
+    // (classify_one's TAIL_EARLY), after pass 1 of the two full chunks, and the next record's trip runs under that.
+    constexpr bool FRONT = LMAT_PREFETCH_ALWAYS && CPT && U == 160 && T == 64 && !INK4 && !WIDE;
     if constexpr (UNI) {
         // UNI: record r is the 16 words from 16 * r -- no offsets to fetch, the next read's words are asked for one read ahead
         static_assert(!UNI || NW == 1, "a UNI record is one wave-load");
         if (it >= A.count) return;
         wcur[0] = ((const GAS uint32_t*)A.words)[kUniRecWords * (A.first + it) + lane];  // (runs past the record: the buffer is padded)
+        if constexpr (FRONT) asm volatile("" : "+v"(wcur[0]));  // the first record is waited for here: the loop header never sees a pending wcur
         while (true) {
             CArgs* Ap = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(Ap));  // (a fresh look at the arguments every trip, as below)
             const uint64_t r = Ap->first + it;
             const bool more = (uint64_t)it + G < Ap->count;
-            wnext[0] = more ? ((const GAS uint32_t*)Ap->words)[kUniRecWords * (r + G) + lane] : 0u;
+            if constexpr (FRONT) {  // asked for on every trip: the last trip asks for the launch's last record again and nobody reads it
+                const uint64_t rn = Ap->first + (more ? (uint64_t)it + G : Ap->count - 1);
+                wnext[0] = ((const GAS uint32_t*)Ap->words)[kUniRecWords * rn + lane];
+            } else {
+                wnext[0] = more ? ((const GAS uint32_t*)Ap->words)[kUniRecWords * (r + G) + lane] : 0u;
+            }
             classify_one<U, T, E, INK4, PERM, CPT, WIDE, PLAIN, UNI>(Ap, r, smem, xl, lane, wcur, nmacc);
             WSYNC();
             wcur[0] = wnext[0];
@@ -4490,9 +4518,17 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
         const GAS uint32_t* words = (const GAS uint32_t*)A.words;
         auto r_of = [&](uint64_t i) -> uint64_t { return index ? (uint64_t)index[i] : A.first + i; };
         const uint64_t off0 = rec_off[r_of(it)];
-        off1 = (uint64_t)it + G < count ? rec_off[r_of((uint64_t)it + G)] : 0;
+        if constexpr (FRONT) {
+            off1 = rec_off[r_of((uint64_t)it + G < count ? (uint64_t)it + G : count - 1)];
+        } else {
+            off1 = (uint64_t)it + G < count ? rec_off[r_of((uint64_t)it + G)] : 0;
+        }
 #pragma unroll
         for (int j = 0; j < NW; ++j) wcur[j] = words[off0 + lane + 64 * j];  // may run past the record: the buffer is padded
+        if constexpr (FRONT) {  // (waited for here, as in the UNI loop)
+#pragma unroll
+            for (int j = 0; j < NW; ++j) asm volatile("" : "+v"(wcur[j]));
+        }
     }
     while (true) {
         CArgs* Ap = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -4502,11 +4538,21 @@ __global__ __launch_bounds__(64, classify_waves(U, E, INK4, CPT)) void classify_
         const GAS uint64_t* rec_off = (const GAS uint64_t*)Ap->rec_off;
         const GAS uint32_t* words = (const GAS uint32_t*)Ap->words;
         auto r_of = [&](uint64_t i) -> uint64_t { return index ? (uint64_t)index[i] : Ap->first + i; };
-        const uint64_t off2 = (uint64_t)it + 2 * (uint64_t)G < count ? rec_off[r_of((uint64_t)it + 2 * (uint64_t)G)] : 0;
+        const uint64_t i2 = (uint64_t)it + 2 * (uint64_t)G;
         const bool more = (uint64_t)it + G < count;
+        uint64_t rcur, off2;
+        if constexpr (FRONT) {
+            rcur = r_of(it);  // (a launch over an index list: this read's entry is waited for before the record is asked for, not behind it)
+            off2 = rec_off[r_of(i2 < count ? i2 : count - 1)];
 #pragma unroll
-        for (int j = 0; j < NW; ++j) wnext[j] = more ? words[off1 + lane + 64 * j] : 0u;
-        classify_one<U, T, E, INK4, PERM, CPT, WIDE, PLAIN>(Ap, r_of(it), smem, xl, lane, wcur, nmacc);
+            for (int j = 0; j < NW; ++j) wnext[j] = words[off1 + lane + 64 * j];
+        } else {
+            off2 = i2 < count ? rec_off[r_of(i2)] : 0;
+#pragma unroll
+            for (int j = 0; j < NW; ++j) wnext[j] = more ? words[off1 + lane + 64 * j] : 0u;
+            rcur = r_of(it);
+        }
+        classify_one<U, T, E, INK4, PERM, CPT, WIDE, PLAIN>(Ap, rcur, smem, xl, lane, wcur, nmacc);
         WSYNC();
 #pragma unroll
         for (int j = 0; j < NW; ++j) wcur[j] = wnext[j];
@@ -4722,6 +4768,9 @@ void classify_variant_launches(int device, uint64_t out[2]) {
     out[1] = g_variant_launches[device][1].load();
 }
 uint64_t classify_uniform_launches(int device) { return device < 0 || device >= 64 ? 0 : g_variant_launches[device][2].load(); }
+// workgroups of the last launch counted above (lmat_debug_classify_grid): a wave takes every grid-th read of the launch
+static std::atomic<uint32_t> g_last_grid[64];
+uint32_t classify_last_grid(int device) { return device < 0 || device >= 64 ? 0 : g_last_grid[device].load(); }
 template <int U, int T, int E, bool INK4, bool PERM, bool CPT, bool WIDE = false, bool PLAIN = false, bool UNI = false>
 static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     using L = WL<U, T, E, INK4, CPT, WIDE>;
@@ -4736,11 +4785,13 @@ static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
             return;
         }
     }
+    int counted_dev = -1;   // the device whose counters took this launch (kPlainClass only)
     if constexpr (kPlainClass) {
         int dev = 0;   // (the current device, asked for as PerDeviceOnce does)
         if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
             g_variant_launches[dev][PLAIN ? 1 : 0]++;
             if (UNI) g_variant_launches[dev][2]++;
+            counted_dev = dev;
         }
     }
     if (U > 2048) {  // tables in global memory: few workgroups; LDS only for the compact probe's scratch block
@@ -4763,6 +4814,7 @@ static void launch_classify_t(const ClassifyArgs& a_in, hipStream_t stream) {
     if (!a.count_ptr && (uint64_t)grid > a.count) grid = (int)a.count;
     if (a.count_ptr && INK4 && grid > 256 * (per_cu < 2 ? 2 : per_cu)) grid = 256 * (per_cu < 2 ? 2 : per_cu);  // the lists of the large classes are short (the E = 512 class may get a tenth of a batch): a block per wave the LDS holds
     if (grid < 1) grid = 1;
+    if (counted_dev >= 0) g_last_grid[counted_dev] = (uint32_t)grid;
     classify_kernel<U, T, E, INK4, PERM, CPT, WIDE, PLAIN, UNI><<<dim3(grid), dim3(64), lds_bytes, stream>>>(a);
 }
 

@@ -126,6 +126,8 @@ void launch_k4_debug_counts(const ClassifyArgs& a, const uint32_t* idx, const ui
 void classify_variant_launches(int device, uint64_t out[2]);
 // ... of those counted under PLAIN, the launches of its UNI variant (records of one geometry)
 uint64_t classify_uniform_launches(int device);
+// ... and the grid of the last launch counted there (0: none yet)
+uint32_t classify_last_grid(int device);
 int classify_max_read_len(int k);   // the longest read of a database of k-mers: kGmemU k-mer positions
 size_t classify_gmem_scratch_bytes();
 // issues ~n_probes random bucket reads (rounded up to 144 per wave x 4096 waves)

@@ -2197,6 +2197,12 @@ int lmat_debug_uniform_launches(lmat_ctx* c, uint64_t* out) {
     *out = classify_uniform_launches(c->device);
     return LMAT_OK;
 }
+// ... and the grid (workgroups of one wave) of the last launch counted in out2: wave b classifies reads b, b + grid, b + 2 grid, ...
+int lmat_debug_classify_grid(lmat_ctx* c, uint32_t* out) {
+    if (!c || !out) return LMAT_E_ARG;
+    *out = classify_last_grid(c->device);
+    return LMAT_OK;
+}
 
 int lmat_last_timing(const lmat_ctx* c, float* classify_ms, float* decide_ms, uint64_t* launches) {
     if (!c) return LMAT_E_ARG;
