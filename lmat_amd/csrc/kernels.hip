@@ -40,11 +40,6 @@
 #ifndef LMAT_TAIL_EARLY
 #define LMAT_TAIL_EARLY 1     // (A/B builds: -DLMAT_TAIL_EARLY=0: a read's tail entries are loaded in the c == 2 arm of pass 1, where they are consumed)
 #endif
-#ifndef LMAT_LDS_SHIFT
-#define LMAT_LDS_SHIFT 0   // (-DLMAT_LDS_SHIFT=1: the lane shifts of the minimizer window and the repeat filter through LDS instead of DPP.
-                           //  Measured in round 4, same box: 24.57 against 24.29 ms per 8 M reads -- 60 vector instructions fewer per read,
-                           //  but two more LDS round trips with their waits in the front end of every read.  Off.)
-#endif
 
 namespace lmat {
 
@@ -2478,30 +2473,21 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
     // with the minimum taken across lanes.  Among equal m-mers cpt_address takes the first in the CANONICAL k-mer's
     // direction, which is the last in the read's direction when the reverse strand is canonical: bits 2..3 of the
     // compared words count positions in that direction.
-    // LSH (the 160-k-mer classes): the m-mer values of the next three positions come out of LDS -- every lane parks its own in an
-    // array over the (dead) packed record, then reads at +1, +2, +3 -- instead of three wave_shl steps: a DPP shift with its
-    // lane-63 patch is a v_readlane, a v_mov and a v_mov_dpp per half and step, 18 vector instructions a chunk, and the vector
-    // pipe is what this kernel runs out of; the LDS pipe has room.  Same for the five wave_shr steps of the repeat filter below.
-    constexpr bool LSH = LMAT_LDS_SHIFT && CACHE && CPT && 8 * (64 * CH + 4) <= WL<U, T, E, INK4, CPT>::XL_BLOOM;
+    // (The three wave_shl steps below, and the five wave_shr steps of the repeat filter, were tried through LDS in round 4 -- every
+    // lane parks its value, then reads its neighbours' -- and measured slower: DESIGN section 3, "Round 4 on the same kernel".)
     auto cpt_finish = [&](int c, uint64_t km, uint64_t u, uint64_t un, uint64_t fcmask, uint32_t& b_out, uint32_t& t_out) {
         const uint32_t ulo = (uint32_t)u, uhi = (uint32_t)(u >> 32);
         uint32_t u1l, u1h, u2l, u2h, u3l, u3h;
-        if constexpr (LSH) {
-            const LAS uint64_t* up = (const LAS uint64_t*)xl + c * 64 + lane;
-            const uint64_t U1 = up[1], U2 = up[2], U3 = up[3];
-            u1l = (uint32_t)U1; u1h = (uint32_t)(U1 >> 32); u2l = (uint32_t)U2; u2h = (uint32_t)(U2 >> 32); u3l = (uint32_t)U3; u3h = (uint32_t)(U3 >> 32);
-        } else {
-            const int n0l = __builtin_amdgcn_readlane((int)(uint32_t)un, 0), n0h = __builtin_amdgcn_readlane((int)(uint32_t)(un >> 32), 0);
-            const int n1l = __builtin_amdgcn_readlane((int)(uint32_t)un, 1), n1h = __builtin_amdgcn_readlane((int)(uint32_t)(un >> 32), 1);
-            const int n2l = __builtin_amdgcn_readlane((int)(uint32_t)un, 2), n2h = __builtin_amdgcn_readlane((int)(uint32_t)(un >> 32), 2);
-            // wave_shl:1 -- lane i takes lane i + 1, lane 63 the next chunk's value
-            u1l = (uint32_t)__builtin_amdgcn_update_dpp(n0l, (int)ulo, 0x130, 0xf, 0xf, false);
-            u1h = (uint32_t)__builtin_amdgcn_update_dpp(n0h, (int)uhi, 0x130, 0xf, 0xf, false);
-            u2l = (uint32_t)__builtin_amdgcn_update_dpp(n1l, (int)u1l, 0x130, 0xf, 0xf, false);
-            u2h = (uint32_t)__builtin_amdgcn_update_dpp(n1h, (int)u1h, 0x130, 0xf, 0xf, false);
-            u3l = (uint32_t)__builtin_amdgcn_update_dpp(n2l, (int)u2l, 0x130, 0xf, 0xf, false);
-            u3h = (uint32_t)__builtin_amdgcn_update_dpp(n2h, (int)u2h, 0x130, 0xf, 0xf, false);
-        }
+        const int n0l = __builtin_amdgcn_readlane((int)(uint32_t)un, 0), n0h = __builtin_amdgcn_readlane((int)(uint32_t)(un >> 32), 0);
+        const int n1l = __builtin_amdgcn_readlane((int)(uint32_t)un, 1), n1h = __builtin_amdgcn_readlane((int)(uint32_t)(un >> 32), 1);
+        const int n2l = __builtin_amdgcn_readlane((int)(uint32_t)un, 2), n2h = __builtin_amdgcn_readlane((int)(uint32_t)(un >> 32), 2);
+        // wave_shl:1 -- lane i takes lane i + 1, lane 63 the next chunk's value
+        u1l = (uint32_t)__builtin_amdgcn_update_dpp(n0l, (int)ulo, 0x130, 0xf, 0xf, false);
+        u1h = (uint32_t)__builtin_amdgcn_update_dpp(n0h, (int)uhi, 0x130, 0xf, 0xf, false);
+        u2l = (uint32_t)__builtin_amdgcn_update_dpp(n1l, (int)u1l, 0x130, 0xf, 0xf, false);
+        u2h = (uint32_t)__builtin_amdgcn_update_dpp(n1h, (int)u1h, 0x130, 0xf, 0xf, false);
+        u3l = (uint32_t)__builtin_amdgcn_update_dpp(n2l, (int)u2l, 0x130, 0xf, 0xf, false);
+        u3h = (uint32_t)__builtin_amdgcn_update_dpp(n2h, (int)u2h, 0x130, 0xf, 0xf, false);
         const bool fc = lane_bit(fcmask);
         // bits 2..3 (free in u): the m-mer's place in the canonical k-mer's direction, 4 i or 12 - 4 i = 4 i ^ 12 -- one xor-add each
         const uint32_t dirm = fc ? 0u : 12u;
@@ -2551,14 +2537,6 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         }
         STOP_AT(47, 0);
         if (CPT) {
-            if constexpr (LSH) {  // every lane's m-mer value, parked for its three left neighbours (the packed record under it is through)
-                WSYNC();
-                LAS uint64_t* ush = (LAS uint64_t*)xl;
-#pragma unroll
-                for (int c = 0; c < CH; ++c) ush[c * 64 + lane] = ureg[c];
-                if (lane < 4) ush[CH * 64 + lane] = 0ull;
-                WSYNC();
-            }
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 if (!UNI && (uint32_t)c * 64 >= P) break;
@@ -2733,44 +2711,20 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
         constexpr uint32_t kNone = 0xFFFFFFFFu;
         uint32_t pb = 0, pq = kNone, ps1 = kNone, ps2 = kNone, ps3 = kNone;
         uint64_t seen = 0;
-        // LSH: bucket, digest and minimizer position of every k-mer parked in LDS (three zero entries in front: nothing precedes
-        // the read), read back at -1, -2, -3
-        LAS uint32_t* barr = (LAS uint32_t*)xl;
-        LAS uint32_t* sarr = barr + (64 * CH + 4);
-        LAS uint16_t* qarr = (LAS uint16_t*)(sarr + (64 * CH + 4));
-        if constexpr (LSH) {
-            static_assert(10 * (64 * CH + 4) <= WL<U, T, E, INK4, CPT>::XL_BLOOM, "the parked values end below the repeat filter's bits");
-            WSYNC();  // (the m-mer values above are through)
-            if (lane < 3) { barr[lane] = 0u; if (DIG) sarr[lane] = kNone; qarr[lane] = 0xFFFF; }
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                if (!UNI && (uint32_t)c * 64 >= P) break;
-                barr[3 + c * 64 + lane] = hreg[c];
-                if (DIG) sarr[3 + c * 64 + lane] = lane_bit(okm[c]) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
-                qarr[3 + c * 64 + lane] = lane_bit(okm[c]) ? (uint16_t)((uint32_t)c * 64 + lane + (treg[c] >> 30)) : (uint16_t)0xFFFF;
-            }
-            WSYNC();
-        }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             if (!UNI && (uint32_t)c * 64 >= P) break;
             const uint64_t V = okm[c];
             const uint32_t b = hreg[c];
             const uint32_t sig = DIG && lane_bit(V) ? (uint32_t)(kreg[c] ^ (kreg[c] >> 17)) : kNone;
-            const uint32_t q = lane_bit(V) ? (uint32_t)c * 64 + lane + (treg[c] >> 30) : (LSH ? 0xFFFFu : kNone);  // where the k-mer's minimizer starts in the read
+            const uint32_t q = lane_bit(V) ? (uint32_t)c * 64 + lane + (treg[c] >> 30) : kNone;  // where the k-mer's minimizer starts in the read
             uint32_t bprev, qprev, s1 = 0, s2 = 0, s3 = 0;
-            if constexpr (LSH) {
-                bprev = barr[c * 64 + lane + 2];
-                qprev = qarr[c * 64 + lane + 2];
-                if constexpr (DIG) { s1 = sarr[c * 64 + lane + 2]; s2 = sarr[c * 64 + lane + 1]; s3 = sarr[c * 64 + lane]; }
-            } else {
-                bprev = (uint32_t)__builtin_amdgcn_update_dpp((int)pb, (int)b, 0x138, 0xf, 0xf, false);  // wave_shr:1
-                qprev = (uint32_t)__builtin_amdgcn_update_dpp((int)pq, (int)q, 0x138, 0xf, 0xf, false);
-                if constexpr (DIG) {
-                    s1 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps1, (int)sig, 0x138, 0xf, 0xf, false);
-                    s2 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps2, (int)s1, 0x138, 0xf, 0xf, false);
-                    s3 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps3, (int)s2, 0x138, 0xf, 0xf, false);
-                }
+            bprev = (uint32_t)__builtin_amdgcn_update_dpp((int)pb, (int)b, 0x138, 0xf, 0xf, false);  // wave_shr:1
+            qprev = (uint32_t)__builtin_amdgcn_update_dpp((int)pq, (int)q, 0x138, 0xf, 0xf, false);
+            if constexpr (DIG) {
+                s1 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps1, (int)sig, 0x138, 0xf, 0xf, false);
+                s2 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps2, (int)s1, 0x138, 0xf, 0xf, false);
+                s3 = (uint32_t)__builtin_amdgcn_update_dpp((int)ps3, (int)s2, 0x138, 0xf, 0xf, false);
             }
             // lane masks, combined on the scalar side: a ballot of `a && b` goes through a 0/1 register and a compare, a ballot of
             // one compare is the compare
@@ -2786,14 +2740,12 @@ __device__ __forceinline__ void classify_one(CArgs* Ap, uint64_t r, unsigned cha
             }
             hitm |= __ballot(both != 0u);
             seen |= hitm;
-            if constexpr (!LSH) {
-                pb = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
-                pq = (uint32_t)__builtin_amdgcn_readlane((int)q, 63);
-                if constexpr (DIG) {
-                    ps1 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 63);
-                    ps2 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 62);
-                    ps3 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 61);
-                }
+            pb =(uint32_t)__builtin_amdgcn_readlane((int)b, 63);
+            pq = (uint32_t)__builtin_amdgcn_readlane((int)q, 63);
+            if constexpr (DIG) {
+                ps1 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 63);
+                ps2 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 62);
+                ps3 = (uint32_t)__builtin_amdgcn_readlane((int)sig, 61);
             }
         }
         suspect = seen != 0;

@@ -8,4 +8,4 @@ N=$1; SRC=$2; shift 2
 O=$ROOT/lmat_amd/csrc
 mkdir -p $ROOT/lmat_amd/variants /tmp/kv
 /opt/rocm/bin/hipcc -std=c++17 -O3 -fPIC -ffp-contract=off --offload-arch=gfx950 -I$O -Wno-unused-result -Wno-unused-function -Wno-unused-value -Wno-pass-failed "$@" -x hip -c $SRC -o /tmp/kv/$N.o &&
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/lmat_amd/variants/$N.so /tmp/kv/$N.o $EXTRA_OBJS $O/dbgen.o $O/kcov.o $O/dbexport.o $O/pairs.o $O/lmat_api.o $O/taxonomy.o $O/dbbuild.o $O/nullmodel.o $O/collective.o -lz -lpthread -ldl && echo built $N
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/lmat_amd/variants/$N.so /tmp/kv/$N.o $EXTRA_OBJS $O/dbgen.o $O/kcov.o $O/dbexport.o $O/pairs.o $O/bins.o $O/lmat_api.o $O/taxonomy.o $O/dbbuild.o $O/nullmodel.o $O/collective.o -lz -lpthread -ldl && echo built $N
